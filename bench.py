@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the FieldConv hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--mode layer|dp|net] [--support p95|all]
+    python bench.py --gpus N --steps K --warmup W [--mode layer|dp|net] [--support p95|all] [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W untimed and K timed steps, and prints the line: value / ms_per_step and the configuration.
+--full adds everything else the line can carry -- the instrumented per-kernel pass (kernels, roofline), the sustained-clock
+repeat (settled), mesh preprocessing and communication figures, the extras (other precisions, the network modes, the
+round-1 mesh, replayed graphs) and the CPU baselines; --cold, --no-kernel-events, --no-extras and --no-cpu-baseline pare it down.
+--dump-outputs DIR writes what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, complex values
+with a trailing (re, im) axis, at most 64 MB in all (larger arrays: a fixed, seeded sample of their rows).
 
 --mode layer (default, the metric of record).  A step = one FieldConv layer forward + backward (input gradient,
 filter-parameter gradients, the filter assembly and its autograd chain included) on a synthetic sphere mesh of
@@ -121,6 +128,48 @@ def cpu_baseline(args, threads, shape=None, slab=4000):
                       f'{t_all:.1f} s'}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, named, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every (name, tensor) as out_dir/<name>.npy -- float64 stays float64, everything else becomes float32,
+    complex values get a trailing (re, im) axis.  Smallest first, each array may take an equal share of what is left of
+    `budget`; one that is larger keeps a fixed, seeded sample of its rows (the same rows for the same shape, run after run).
+    -> {name: shape written}"""
+    import numpy as np
+    arrays = []
+    for name, t in named:
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu()
+        arrays.append((name, t.numpy().reshape(t.shape or (1,))))
+    os.makedirs(out_dir, exist_ok=True)
+    written, left = {}, budget
+    arrays.sort(key=lambda na: na[1].nbytes)
+    for i, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+        written[name] = list(a.shape)
+        left -= a.nbytes
+    return written
+
+
+def dump_callback(args, rank, outputs):
+    """timed_loop's after_literal for --dump-outputs (None without it): rank 0 writes outputs(), a list of (name, tensor)."""
+    if not args.dump_outputs:
+        return None
+
+    def write():
+        if rank == 0:
+            write_outputs(args.dump_outputs, outputs())
+    return write
+
+
 def env_report():
     """Every development switch of the package / the library / this script that is set in this process (fieldconv_amd/_env.py)."""
     from fieldconv_amd import _env
@@ -144,7 +193,7 @@ def child_run(args, env_extra, extra_args=(), dump=True):
         path = os.path.join(tmp, 'out.pt')
         cmd = [sys.executable, os.path.abspath(__file__), '--steps', str(args.steps), '--warmup', str(args.warmup),
                '--verts', str(args.verts), '--k', str(args.k), '--channels', str(args.channels), '--band-limit',
-               str(args.band_limit), '--n-rings', str(args.n_rings), '--support', args.support, '--no-cpu-baseline', '--no-extras']
+               str(args.band_limit), '--n-rings', str(args.n_rings), '--support', args.support, '--full', '--no-cpu-baseline', '--no-extras']
         cmd += list(extra_args)
         if dump:
             cmd += ['--dump', path]
@@ -170,10 +219,10 @@ def other_mode(args, env_extra, what, y, gx):
 
 
 def mode_leg(mode, keep):
-    """`python bench.py --mode <mode>` (25 steps after 5, with its own bounded CPU baseline) in a child process -> the compact form of
+    """`python bench.py --mode <mode> --full` (25 steps after 5, with its own bounded CPU baseline) in a child process -> the compact form of
     its line: value, ms per step (literal and settled), dominant-kernel roofline fraction, CPU baseline, and the extras named in `keep`."""
     try:
-        cmd = [sys.executable, os.path.abspath(__file__), '--mode', mode, '--steps', '25', '--warmup', '5']
+        cmd = [sys.executable, os.path.abspath(__file__), '--mode', mode, '--steps', '25', '--warmup', '5', '--full']
         env = {k_: v for k_, v in os.environ.items() if not k_.startswith('FC_')}
         res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
         line = json.loads(res.stdout.strip().splitlines()[-1])
@@ -252,8 +301,10 @@ PROTOCOL_NOTE = ('value / ms_per_step: literally the command line -- `warmup` un
                  'run lives at; reported beside it, never as value (--cold skips it)')
 
 
-def timed_loop(step, steps, warmup, use_dist, dev, backend, before_timed=None, after_timed=None, settle=True, head_start_cycles=0):
-    """-> (seconds for `steps` steps under the LITERAL protocol, max over ranks; info).
+def timed_loop(step, steps, warmup, use_dist, dev, backend, before_timed=None, after_timed=None, settle=True, head_start_cycles=0,
+               after_literal=None):
+    """-> (seconds for `steps` steps under the LITERAL protocol, max over ranks; info).  after_literal() runs straight behind the
+    literal region's closing fence, before any other step (--dump-outputs reads the last timed step's results there).
 
     The literal protocol -- `warmup` steps, fence, `steps` steps, fence, as the first GPU work of the process -- is the value
     of record and carries NO instrumentation.  The MI355X's clock governor takes ~100 ms of sustained load to reach the clock
@@ -281,6 +332,8 @@ def timed_loop(step, steps, warmup, use_dist, dev, backend, before_timed=None, a
             step()
         fence()
         elapsed = time.perf_counter() - t0
+        if tag == 'literal' and after_literal is not None:
+            after_literal()
         if before_timed is not None:            # the instrumented pass: same steps, event pairs on a sample of the launches, untimed
             before_timed()
             if head_start_cycles:
@@ -430,6 +483,7 @@ def run_dp(args, world, rank, dev, use_dist, backend):
     pos = torch.randn(N, 3, generator=g).to(dev)
     labels = torch.randint(0, n_cls, (N,), generator=g).to(dev)
     n_convs = 2 * len(blocks) + 1
+    keep = {} if args.dump_outputs else None                  # the last step's loss, detached (no autograd graph is kept alive)
 
     def step():
         edges, sten, ln, wxp = pre(data)                       # runs every forward in the reference, too (memoised per mesh)
@@ -451,6 +505,8 @@ def run_dp(args, world, rank, dev, use_dist, backend):
         buckets.collect()                                      # ... one multi-tensor copy packs them into the flat buffer
         if use_dist:
             buckets.all_reduce()                               # the one collective of a data-parallel step
+        if keep is not None:
+            keep['loss'] = loss.detach()
         return loss
 
     from fieldconv_amd.functional import kernel_timer
@@ -469,8 +525,10 @@ def run_dp(args, world, rank, dev, use_dist, backend):
         kernel_timer.enabled = False
         harvested[tag] = {k_: sum(v) / len(v) for k_, v in kernel_timer.elapsed_ms().items() if v}
 
+    # (the parameters' .grad are views into the flat buffer, all-reduced with several ranks)
+    dump = dump_callback(args, rank, lambda: [('loss', keep['loss'])] + [('grad_' + n, p.grad) for n, p in net.named_parameters()])
     elapsed, info = timed_loop(step, args.steps, args.warmup, use_dist, dev, backend, before_timed=None if args.no_kernel_events else arm_timer, after_timed=harvest,
-                               settle=not args.cold, head_start_cycles=4_000_000)
+                               settle=not args.cold, head_start_cycles=4_000_000, after_literal=dump)
     E_total = sum_over_ranks(E, use_dist, dev, backend)
     identity = run_identity(use_dist, dev, backend, dev.index, {'vertices': N, 'edges': E})
     if rank != 0:
@@ -625,15 +683,22 @@ def run_net(args, world, rank, dev, use_dist, backend):
         logits = net['echo'](x, edges, sten, ln, wxp)
         return torch.nn.functional.nll_loss(torch.nn.functional.log_softmax(logits, dim=1), lab)
 
+    keep = {} if args.dump_outputs else None                  # the last step's loss (detached) and parameter gradients
+
     def step():
         loss = forward_loss(data, pos, labels)
         if buckets is None:
-            return (loss,) + torch.autograd.grad(loss, params)
-        buckets.begin()
-        loss.backward()
-        buckets.collect()
-        buckets.all_reduce()
-        return (loss,)
+            res = (loss,) + torch.autograd.grad(loss, params)
+        else:
+            buckets.begin()
+            loss.backward()
+            buckets.collect()
+            buckets.all_reduce()
+            res = (loss,)
+        if keep is not None:
+            keep['loss'] = loss.detach()
+            keep['grads'] = res[1:] if buckets is None else tuple(p.grad for p in params)
+        return res
 
     E = int(pre(data)[0].shape[0])
     harvested = {}
@@ -650,8 +715,9 @@ def run_net(args, world, rank, dev, use_dist, backend):
         kernel_timer.enabled = False
         harvested[tag] = {k_: sum(v) / len(v) for k_, v in kernel_timer.elapsed_ms().items() if v}
 
+    dump = dump_callback(args, rank, lambda: [('loss', keep['loss'])] + [('grad_' + n, g) for (n, _), g in zip(net.named_parameters(), keep['grads'])])
     elapsed, info = timed_loop(step, args.steps, args.warmup, use_dist, dev, backend, before_timed=None if args.no_kernel_events else arm_timer, after_timed=harvest,
-                               settle=not args.cold, head_start_cycles=4_000_000)
+                               settle=not args.cold, head_start_cycles=4_000_000, after_literal=dump)
     E_total = sum_over_ranks(E, use_dist, dev, backend)
     identity = run_identity(use_dist, dev, backend, dev.index, {'vertices': N, 'edges': E})
     if rank != 0:
@@ -791,17 +857,23 @@ def run_layer(args, world, rank, dev, use_dist, backend):
         overlap_forward(mesh_graph, plan, n_interior)       # interior targets are convolved while the halo rows travel
     split_fwd = mesh_graph.forward_split is not None and 0 < mesh_graph.forward_split[0] < n_local      # two forward launches per step
 
+    keep = {} if args.dump_outputs else None                 # the last step's output (detached) and gradients
+
     def step():
         xl = halo_exchange(x, plan, deferred=overlap_fwd) if plan is not None else x
         y = conv(xl, edges, sten)
         if buckets is None:
-            return torch.autograd.grad(y, [x] + params, grad_outputs=gy)
-        buckets.begin()
-        x.grad = None
-        y.backward(gy)
-        buckets.collect()
-        buckets.all_reduce()
-        return (x.grad,) + tuple(p.grad for p in params)
+            res = torch.autograd.grad(y, [x] + params, grad_outputs=gy)
+        else:
+            buckets.begin()
+            x.grad = None
+            y.backward(gy)
+            buckets.collect()
+            buckets.all_reduce()
+            res = (x.grad,) + tuple(p.grad for p in params)
+        if keep is not None:
+            keep['y'], keep['grads'] = y.detach(), res
+        return res
 
     # Opt-in (BENCH_GRAPH_STEP=1): the whole partitioned step -- both halo exchanges, the convolution's kernels, the bucketed
     # all-reduce -- captured once in ONE HIP graph and replayed (RCCL's collectives are capturable through torch's NCCL
@@ -850,8 +922,10 @@ def run_layer(args, world, rank, dev, use_dist, backend):
         if not graph_step:
             harvested[tag] = {k_: sum(v) / len(v) for k_, v in kernel_timer.elapsed_ms().items() if v}
 
+    dump = dump_callback(args, rank, lambda: [('y', keep['y']), ('grad_x', keep['grads'][0])] +
+                         [('grad_' + n, g) for (n, _), g in zip(conv.named_parameters(), keep['grads'][1:])])
     elapsed, info = timed_loop(step, args.steps, args.warmup, use_dist, dev, backend, before_timed=None if args.no_kernel_events else arm_timer, after_timed=harvest,
-                               settle=not args.cold)
+                               settle=not args.cold, after_literal=dump)
     if graph_step:                          # per-kernel times from a few eager steps behind the timed regions
         kernel_timer.reset(pairs=64)
         kernel_timer.stride = 1
@@ -902,7 +976,7 @@ def run_layer(args, world, rank, dev, use_dist, backend):
         return comm
 
     comm = None
-    if use_dist and not graph_step:
+    if use_dist and not graph_step and args.full:
         hooks = (mesh_graph.on_gx, mesh_graph.forward_split)
         try:        # (an extra: whatever goes wrong here on a first multi-rank RCCL run must not cost the line its value)
             comm = measure_comm()
@@ -911,7 +985,7 @@ def run_layer(args, world, rank, dev, use_dist, backend):
             comm = {'error': f'{type(exc).__name__}: {exc}'[:300]}
     identity = run_identity(use_dist, dev, backend, dev.index, {'owned_vertices': int(n_owned), 'halo_rows': 0 if plan is None else plan.n_halo,
                                                                  'edges': E})
-    prep_ms, prep_mallocs = measure_prep()
+    prep_ms, prep_mallocs = measure_prep() if args.full else (None, None)
     if rank != 0:
         return None
 
@@ -1116,7 +1190,16 @@ def main():
     ap.add_argument('--no-extras', action='store_true', help='only the metric of record (used by the child runs)')
     ap.add_argument('--no-kernel-events', action='store_true', help='no instrumented pass behind the timed region (roofline: null) -- for runs under a profiler')
     ap.add_argument('--dump', default=None, help='write y and gx of one step to this file (child runs)')
+    ap.add_argument('--full', action='store_true', help='everything besides value / ms_per_step as well: instrumented per-kernel pass '
+                    '(kernels, roofline), settled repeat, preprocessing and communication figures, extras, CPU baselines')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write what the last timed step returned to DIR/<name>.npy '
+                    '(float32 / float64, at most 64 MB in all)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if not args.full:
+        # a plain run: setup, warm-up, the timed steps, the line -- nothing that takes runs of its own
+        args.cold = args.no_kernel_events = args.no_extras = args.no_cpu_baseline = True
 
     # Development switches of the library change what is computed (FC_DEBUG* skip whole phases): a benchmark line taken
     # with one of them set would be wrong or mislabelled, so it is refused outright.

@@ -76,7 +76,7 @@ def test_parity_subset_in_mode(mode):
 def test_bench_partitioned_step_as_one_hip_graph():
     """BENCH_GRAPH_STEP=1: halo exchanges, convolution kernels and the bucketed all-reduce of the partitioned step captured in
     one HIP graph (single rank over RCCL) -- the line is produced and the step is not slower than the eager one."""
-    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5', '--verts', '6000', '--no-cpu-baseline',
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5', '--verts', '6000', '--full', '--no-cpu-baseline',
             '--no-extras', '--cold']
     out = {}
     for flag in ('0', '1'):
@@ -145,7 +145,7 @@ def test_bench_starts_its_own_ranks_from_the_plain_command_line():
 
 def test_bench_line_is_the_literal_protocol():
     """value / ms_per_step come from the first warmup + steps of the process; the sustained-clock repeat is the `settled` extra."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--verts', '3000', '--no-cpu-baseline',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--verts', '3000', '--full', '--no-cpu-baseline',
            '--no-extras']
     res = subprocess.run(cmd, cwd=ROOT, env=_clean_env({}), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -155,10 +155,36 @@ def test_bench_line_is_the_literal_protocol():
     assert line['roofline']['frac'] > 0 and line['roofline']['avg_launch_ms'] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries value / ms_per_step of the literal protocol and nothing that takes runs of its own;
+    --dump-outputs writes the last timed step's output and gradients, and two runs with the same arguments agree."""
+    import numpy as np
+    dumped = []
+    for run in range(2):
+        out_dir = str(tmp_path / f'run{run}')
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--verts', '3000', '--dump-outputs', out_dir]
+        res = subprocess.run(cmd, cwd=ROOT, env=_clean_env({}), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = json.loads(res.stdout.strip().splitlines()[-1])
+        assert line['warmup'] == 2 and line['steps'] == 4 and line['value'] > 0 and line['ms_per_step'] > 0
+        assert line['unit'] == 'Medges/s' and line['higher_is_better'] is True and line['dtype']
+        assert line['settled'] is None and line['roofline'] is None and line['kernels'] == {} and line['cpu_baseline'] is None
+        assert line['mesh_preprocessing_ms'] is None and 'fp32_mfma' not in line and 'config3_segmentation_net' not in line
+        files = {f[:-4]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)}
+        assert set(files) == {'y', 'grad_x', 'grad_zonal', 'grad_spherical', 'grad_phase'}, sorted(files)
+        assert files['y'].shape == (3000, 48, 2) and files['grad_x'].shape == (3000, 48, 2)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0 for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        dumped.append(files)
+    for name, a in dumped[0].items():
+        b = dumped[1][name]
+        assert float(np.abs(a - b).max()) <= 1e-5 * float(np.abs(b).max()), name
+
+
 def test_bench_data_parallel_mode_single_rank():
     """bench.py --mode dp (BASELINE configs[4]: one mesh per rank, replicated net, one bucketed all-reduce) with a
     single rank over RCCL."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--mode', 'dp', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--mode', 'dp', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline',
            '--no-extras']
     env = _clean_env({'BENCH_FORCE_DIST': '1', 'MASTER_ADDR': '127.0.0.1', 'MASTER_PORT': '29532', 'RANK': '0', 'WORLD_SIZE': '1',
                       'LOCAL_RANK': '0'})
@@ -173,7 +199,7 @@ def test_bench_segmentation_net_mode():
     """bench.py --mode net (BASELINE configs[2]: the segmentation network's topology on a 1 024-vertex mesh, launched eagerly through the
     block-level entry points): the line carries roofline, the replayed-graph figure, the host's enqueue time and the per-operator
     comparison, and the eager step is not host-bound by more than a third."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--mode', 'net', '--steps', '10', '--warmup', '5', '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--mode', 'net', '--steps', '10', '--warmup', '5', '--full', '--no-cpu-baseline']
     res = subprocess.run(cmd, cwd=ROOT, env=_clean_env({}), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])

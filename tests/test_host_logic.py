@@ -446,6 +446,38 @@ def test_kernel_description_and_gpu_count_need_no_gpu():
                 os.environ[k] = v
 
 
+def test_bench_dump_writes_float_arrays_within_its_budget(tmp_path):
+    """bench.py --dump-outputs: complex tensors as float32 (re, im) pairs, float64 kept, a scalar as one element; past the byte
+    budget the large arrays keep a fixed, seeded sample of their rows.  --steps below 1 is refused before any work."""
+    import importlib.util
+    import subprocess
+    import sys
+    spec = importlib.util.spec_from_file_location('bench_module', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    y = torch.complex(torch.randn(1000, 8, generator=g), torch.randn(1000, 8, generator=g))
+    named = [('y', y), ('grad_w', torch.randn(3, 4, generator=g)), ('loss', torch.tensor(1.5)),
+             ('d', torch.randn(10, generator=g, dtype=torch.float64))]
+    budget = 20000
+    shapes = bench.write_outputs(str(tmp_path / 'a'), named, budget=budget)
+    files = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in shapes}
+    assert files['grad_w'].dtype == np.float32 and files['grad_w'].shape == (3, 4)
+    assert files['loss'].shape == (1,) and files['loss'][0] == 1.5
+    assert files['d'].dtype == np.float64 and np.array_equal(files['d'], named[3][1].numpy())
+    full = torch.view_as_real(y).numpy()
+    ys = files['y']
+    assert ys.dtype == np.float32 and ys.shape[1:] == (8, 2) and 0 < ys.shape[0] < 1000
+    assert sum(a.nbytes for a in files.values()) <= budget
+    rows = [int(np.nonzero((full == r).all(axis=(1, 2)))[0][0]) for r in ys]
+    assert rows == sorted(set(rows))                     # distinct rows of the array, in order
+    bench.write_outputs(str(tmp_path / 'b'), named, budget=budget)
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'y.npy')), ys)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True, timeout=300)
+    assert res.returncode == 2 and '--steps' in res.stderr and res.stdout.strip() == ''
+
+
 def test_graph_views_keep_the_cached_graph_clean():
     """get_graph hands every user of a mesh the same cached SupportGraph: target restrictions and exchange hooks go on a view
     (own hooks and plans, shared arrays), which reaches the modules through FactoredStencil.wrap."""

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 # build first, from a process no profiler has touched (bench.py refuses to build under rocprofv3)
 python3 -c "import sys; sys.path.insert(0, '$ROOT'); import __graft_entry__; __graft_entry__.build()" || exit 1
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $ROOT/bench.py --no-cpu-baseline --no-extras --steps 40 --warmup 10"
+CMD="python3 $ROOT/bench.py --full --no-cpu-baseline --no-extras --steps 40 --warmup 10"
 rm -rf /tmp/pb_*
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb_stats -o p -- $CMD > "$OUT/${TAG}_bench_under_rocprof.json" 2>/dev/null
 cp /tmp/pb_stats/*kernel_stats.csv "$OUT/${TAG}_kernel_stats.csv" 2>/dev/null || cp $(find /tmp/pb_stats -name '*kernel_stats.csv' | head -1) "$OUT/${TAG}_kernel_stats.csv"
@@ -60,7 +60,7 @@ for short, cands in names.items():
             if k in avg_ns:
                 e['rocprof_avg_us'] = avg_ns[k] / 1e3
             res[short] = e
-json.dump({'library_source_digest': _source_digest(), 'command': 'python3 bench.py --no-cpu-baseline --no-extras --steps 40 --warmup 10',
+json.dump({'library_source_digest': _source_digest(), 'command': 'python3 bench.py --full --no-cpu-baseline --no-extras --steps 40 --warmup 10',
            'formulas': 'launch_cycles = SQ_BUSY_CYCLES / 32 shader engines; valu_busy = 4 * SQ_ACTIVE_INST_VALU / (1024 SIMDs * launch_cycles); '
                        'mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 * launch_cycles); HBM read = 2 * FETCH_SIZE KiB (gfx950 calibration for '
                        'wide streaming reads; narrower gathers are uncalibrated: upper estimate), write = WRITE_SIZE KiB',

@@ -10,10 +10,10 @@ mkdir -p "$OUT"
 cd "$ROOT"
 bash tools/profile_bench.sh "$TAG" > "$OUT/${TAG}_profile_bench.log" 2>&1
 cp "$OUT/${TAG}_pmc_counters.json" "$ROOT/profiles/pmc_counters.json"
-python3 bench.py --steps 20 --warmup 5 > "$OUT/${TAG}_bench_driver_protocol.json" 2> "$OUT/${TAG}_bench_driver_protocol.err"
-python3 bench.py --no-cpu-baseline --no-extras > "$OUT/${TAG}_bench_default.json" 2> /dev/null
-python3 bench.py --mode dp --steps 20 --warmup 5 > "$OUT/${TAG}_bench_dp.json" 2> /dev/null
-python3 bench.py --mode net --steps 20 --warmup 5 > "$OUT/${TAG}_bench_net.json" 2> /dev/null
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/${TAG}_bench_driver_protocol.json" 2> "$OUT/${TAG}_bench_driver_protocol.err"
+python3 bench.py --full --no-cpu-baseline --no-extras > "$OUT/${TAG}_bench_default.json" 2> /dev/null
+python3 bench.py --full --mode dp --steps 20 --warmup 5 > "$OUT/${TAG}_bench_dp.json" 2> /dev/null
+python3 bench.py --full --mode net --steps 20 --warmup 5 > "$OUT/${TAG}_bench_net.json" 2> /dev/null
 bash tools/prof_net.sh > "$OUT/${TAG}_net_prof.log" 2>&1
 bash tools/prof_dp.sh > "$OUT/${TAG}_dp_prof.log" 2>&1
 head -c 400 "$OUT/${TAG}_bench_driver_protocol.json"; echo
