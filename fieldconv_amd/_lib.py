@@ -169,6 +169,12 @@ SIGNATURES = {
     'fc_lift_block_workspace_bytes': (_sz, [_MP, _LBP, _c_int32]),
     'fc_lift_block_forward': (ctypes.c_int, [_vp, _vp, _c_int32, _MP, _vp, _LBP, _vp, _vp, _sz, _vp]),
     'fc_lift_block_backward': (ctypes.c_int, [_vp, _vp, _c_int32, _MP, _vp, _LBP, _vp, _sz, _vp, _vp, _sz, _vp]),
+    'fc_fps_workspace_bytes': (_sz, [_c_int32]),
+    'fc_fps': (ctypes.c_int, [_vp, _c_int32, _c_int32, _c_int32, _vp, _vp, _sz, _vp]),
+    'fc_radius_workspace_bytes': (_sz, [_c_int32]),
+    'fc_radius_count': (ctypes.c_int, [_vp, _c_int32, ctypes.c_float, _c_int32, _vp, _sz, _vp]),
+    'fc_radius_edge_count_ptr': (_vp, [_vp, _c_int32]),
+    'fc_radius_fill': (ctypes.c_int, [_vp, _c_int32, ctypes.c_float, _c_int32, ctypes.c_int64, _vp, _vp, _sz, _vp]),
 }
 
 _LIB = None

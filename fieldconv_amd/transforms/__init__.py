@@ -1,4 +1,7 @@
 from .fc_precomp import FCPrecomp
+from .normalize import NormalizeArea, NormalizeAxes
 from .precomp_cache import load_precomp, save_precomp
+from .support_graph import SupportGraph, farthest_point_sample, radius_edges
 
-__all__ = ['FCPrecomp', 'load_precomp', 'save_precomp']
+__all__ = ['FCPrecomp', 'NormalizeArea', 'NormalizeAxes', 'SupportGraph', 'farthest_point_sample', 'load_precomp', 'radius_edges',
+           'save_precomp']

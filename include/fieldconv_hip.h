@@ -548,6 +548,28 @@ int fc_precomp_graph(const float* log_mag, const float* log_ang, const float* xp
 int fc_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step, size_t n, float lr,
                  float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ---- support graph (the reference's SupportGraph transform: farthest-point sampling, then a radius search) ---------- *
+ * Distances: d2 = (dx*dx + dy*dy) + dz*dz in fp32 with dx = p_n.x - p_q.x, every operation rounded on its own (no fused
+ * multiply-add), in both searches.  pos: (N,3) float32, contiguous, device memory.
+ * fc_fps             idx (n_samples) int64 in selection order, idx[0] = start; each round takes the unselected point with the
+ *                    largest min over selected s of d2(i, s), ties to the lowest index; a point is never taken twice.
+ *                    1 <= n_samples <= N, 0 <= start < N.  One workgroup; workspace: fc_fps_workspace_bytes(N).
+ * fc_radius_count    enqueues the per-query counts of the points n with d2(q, n) < r2, r2 = epsilon * epsilon in fp32 (q itself
+ *                    included), capped at max_num_neighbors = K, and their scan; afterwards fc_radius_edge_count_ptr() points
+ *                    at the device int64 E, the number of rows (the caller's one synchronisation reads it).
+ * fc_radius_fill     with the same workspace, writes supp_edges (E,2) int64 [q, n]: queries ascending, each query's
+ *                    neighbours ascending; a query with more than K qualifying points keeps the K smallest (d2, n).
+ * epsilon must be positive and finite, K >= 1.  No allocation or synchronisation inside. */
+size_t fc_fps_workspace_bytes(int32_t N);
+int fc_fps(const float* pos, int32_t N, int32_t n_samples, int32_t start, int64_t* idx, void* workspace, size_t workspace_bytes,
+           void* stream);
+size_t fc_radius_workspace_bytes(int32_t N);
+int fc_radius_count(const float* pos, int32_t N, float epsilon, int32_t max_num_neighbors, void* workspace, size_t workspace_bytes,
+                    void* stream);
+const int64_t* fc_radius_edge_count_ptr(const void* workspace, int32_t N);
+int fc_radius_fill(const float* pos, int32_t N, float epsilon, int32_t max_num_neighbors, int64_t E, int64_t* supp_edges,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
