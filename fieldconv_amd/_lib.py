@@ -175,6 +175,18 @@ SIGNATURES = {
     'fc_radius_count': (ctypes.c_int, [_vp, _c_int32, ctypes.c_float, _c_int32, _vp, _sz, _vp]),
     'fc_radius_edge_count_ptr': (_vp, [_vp, _c_int32]),
     'fc_radius_fill': (ctypes.c_int, [_vp, _c_int32, ctypes.c_float, _c_int32, ctypes.c_int64, _vp, _vp, _sz, _vp]),
+    'fc_pair_sqdist': (ctypes.c_int, [_vp, _c_int32, _vp, _c_int32, _c_int32, _c_int32, _vp, ctypes.c_int64, _vp, _vp]),
+    'fc_twin_loss_workspace_bytes': (_sz, [ctypes.c_int64, ctypes.c_int64]),
+    'fc_twin_loss_forward': (ctypes.c_int, [_vp, _c_int32, _vp, _c_int32, _c_int32, _c_int32, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp,
+                                            ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
+    'fc_twin_loss_backward': (ctypes.c_int, [_vp, _c_int32, _vp, _c_int32, _c_int32, _c_int32, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp,
+                                             ctypes.c_double] + [_vp] * 8 + [_vp]),
+    'fc_twin_count_dense': (ctypes.c_int, [_vp, _c_int32, _vp, _c_int32, _c_int32, _c_int32, ctypes.POINTER(ctypes.c_double), _c_int32, _vp, _vp]),
+    'fc_label_smoothing_workspace_bytes': (_sz, [ctypes.c_int64, _c_int32]),
+    'fc_label_smoothing_forward': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _c_int32, _c_int32, ctypes.c_double, ctypes.c_double, _vp, _vp,
+                                                  _sz, _vp]),
+    'fc_label_smoothing_backward': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _c_int32, _c_int32, ctypes.c_double, ctypes.c_double,
+                                                   _vp, _vp]),
 }
 
 _LIB = None

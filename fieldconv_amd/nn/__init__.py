@@ -7,6 +7,9 @@ from .echo import ECHO
 from .lift_block import LiftBlock
 from .fc_resnet_block import FCResNetBlock
 from .echo_block import ECHOBlock
+from .label_smoothing_loss import LabelSmoothingLoss
+from .twin_loss import TwinLoss
+from .twin_eval import TwinEval
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
-           'FCResNetBlock', 'ECHOBlock']
+           'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval']

@@ -570,6 +570,47 @@ const int64_t* fc_radius_edge_count_ptr(const void* workspace, int32_t N);
 int fc_radius_fill(const float* pos, int32_t N, float epsilon, int32_t max_num_neighbors, int64_t E, int64_t* supp_edges,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- losses (the reference's TwinLoss, TwinEval, LabelSmoothingLoss) and the pair kernels under them ------------------ *
+ * Features: xS (N_S,C) and xT (N_T,C), row-major, contiguous, device memory, real; dtype 0 = float32, 1 = float64 (every
+ * device scalar and array of the call then has that type).  Pair lists: (K,2) int64 rows [row of xT, row of xS].
+ * Distance: d2(a,b) = ((t0*t0 + t1*t1) + t2*t2) + ... with t_c = xT[a,c] - xS[b,c], c ascending, every operation rounded on
+ * its own (no fused multiply-add); all four pair kernels produce the same bits for the same pair.  Sums that end in one
+ * scalar run in double in a fixed order: two runs give the same bits.  Rows within N < 2^24 and N*C*8 < 4 GiB.
+ * pair sqdist         d2 (K) for a pair list whose indices the CALLER has checked (the kernel does not).
+ * twin loss forward   loss[0] = sum_k d2(p_k) / P + sum_k (yN_k d2(n_k) + (1 - yN_k) max(mu - d2(n_k), 0)) / M, and
+ *                     d2 (P + M): the positives' distances, then the negatives', saved for the backward pass.  A pair with an
+ *                     index outside [0,N_T) x [0,N_S) reads nothing and counts as NaN.  P, M >= 1.  yN (M) is float32 for either
+ *                     dtype, and 1 - yN_k is rounded in float32 before it is widened (the reference draws float32 weights).
+ * twin loss backward  grad_xT[a] = sum over the pairs k at row a of c_k t, grad_xS[b] = -sum c_k t, t = xT[a] - xS[b],
+ *                     c_k = 2 g / P (positives), 2 g (yN_k - (1 - yN_k) [mu - d2_k > 0]) / M (negatives), g = grad_loss[0].
+ *                     Pairs are numbered p_ first, then n_ (k in [0, P + M)).  order_T (P + M): the pair numbers sorted
+ *                     stably by their xT row; rowptr_T (N_T + 1): row a owns order_T[rowptr_T[a] .. rowptr_T[a + 1]);
+ *                     likewise order_S / rowptr_S by xS row.  Each row sums its pairs in that order (no atomics) and every
+ *                     row of the dense (N,C) gradients is written, zeros where no pair touches it.
+ * twin count dense    over ALL pairs (a,b) in [0,N_T) x [0,N_S): counts[t] = #{d2 < thr_t}, counts[T + t] = #{d2 > thr_t} for
+ *                     T = n_thresholds in [1,16]; thresholds is a HOST array, each value rounded to dtype.  counts: 2T device int64.
+ * label smoothing     pred (N,K), target (N) int64, weight (K) or null: loss[0] = mean_n sum_k -t_nk w_k log_softmax(pred_n)_k
+ *                     with t_nk = confidence at k = target_n and off_value elsewhere; backward recomputes the softmax:
+ *                     grad_pred[n,j] = (g / N) (softmax_nj sum_k t_nk w_k - t_nj w_j).  A target outside [0,K) selects no class.
+ * Workspaces: the *_workspace_bytes queries (per-workgroup partial sums).  No allocation or synchronisation inside. */
+int fc_pair_sqdist(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int32_t C, int32_t dtype, const int64_t* pairs, int64_t K,
+                   void* d2, void* stream);
+size_t fc_twin_loss_workspace_bytes(int64_t P, int64_t M);
+int fc_twin_loss_forward(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int32_t C, int32_t dtype, const int64_t* p_, int64_t P,
+                         const int64_t* n_, int64_t M, const void* yN, double mu, void* d2, void* loss, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int fc_twin_loss_backward(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int32_t C, int32_t dtype, const int64_t* p_, int64_t P,
+                          const int64_t* n_, int64_t M, const void* yN, double mu, const void* d2, const void* grad_loss,
+                          const int64_t* rowptr_T, const int64_t* order_T, const int64_t* rowptr_S, const int64_t* order_S, void* grad_xT,
+                          void* grad_xS, void* stream);
+int fc_twin_count_dense(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int32_t C, int32_t dtype, const double* thresholds,
+                        int32_t n_thresholds, int64_t* counts, void* stream);
+size_t fc_label_smoothing_workspace_bytes(int64_t N, int32_t K);
+int fc_label_smoothing_forward(const void* pred, const int64_t* target, const void* weight, int64_t N, int32_t K, int32_t dtype,
+                               double confidence, double off_value, void* loss, void* workspace, size_t workspace_bytes, void* stream);
+int fc_label_smoothing_backward(const void* pred, const int64_t* target, const void* weight, const void* grad_loss, int64_t N, int32_t K,
+                                int32_t dtype, double confidence, double off_value, void* grad_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
