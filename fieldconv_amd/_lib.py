@@ -187,6 +187,15 @@ SIGNATURES = {
                                                   _sz, _vp]),
     'fc_label_smoothing_backward': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _c_int32, _c_int32, ctypes.c_double, ctypes.c_double,
                                                    _vp, _vp]),
+    'fc_fps_batched_workspace_bytes': (_sz, [_c_int32]),
+    'fc_fps_batched': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _sz, _vp]),
+    'fc_radius_count_batched': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, ctypes.c_float, _c_int32, _vp, _sz, _vp]),
+    'fc_radius_fill_batched': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, ctypes.c_float, _c_int32, ctypes.c_int64, _vp, _vp, _sz, _vp]),
+    'fc_segment_pool_workspace_bytes': (_sz, [_c_int32] * 4),
+    'fc_segment_pool_soft_abs_forward': (ctypes.c_int, [_vp, _vp] + [_c_int32] * 5 + [_vp, _vp, _sz, _vp]),
+    'fc_segment_pool_soft_abs_backward': (ctypes.c_int, [_vp, _vp, _vp] + [_c_int32] * 5 + [_vp, _vp]),
+    'fc_segment_pool_forward': (ctypes.c_int, [_vp, _vp] + [_c_int32] * 5 + [_vp, _vp, _sz, _vp]),
+    'fc_segment_pool_backward': (ctypes.c_int, [_vp, _vp] + [_c_int32] * 5 + [_vp, _vp]),
 }
 
 _LIB = None

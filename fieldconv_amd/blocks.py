@@ -2,7 +2,7 @@
 
 The reference's networks are stacks of three blocks -- FCResNetBlock (reference nn/fc_resnet_block.py:65-88), ECHOBlock
 (nn/echo_block.py:73-103), LiftBlock (nn/lift_block.py:35-55) -- trained with batch size 1 on a different ~1k-vertex mesh every step
-(segmentation.ipynb:120,137).  At that size the GPU runs a block in ~150 us while a per-operator binding spends ~300 us of host time on
+(segmentation.ipynb:120,137; several meshes per step: fieldconv_amd.data.MeshBatch).  At that size the GPU runs a block in ~150 us while a per-operator binding spends ~300 us of host time on
 it: five autograd nodes, a dozen `torch.empty`, sixteen ctypes calls.  The functions below hand a whole block pass to the library's
 block-level entry points (csrc/fc_blocks.hip: fc_resnet_block_forward / _backward, fc_echo_block_*, fc_lift_block_*): same kernels, same
 bits, two foreign calls and two allocations per pass.

@@ -2,6 +2,9 @@
 //   fc_fps                       farthest-point sampling, one 1024-thread workgroup, one dependent argmax round per sample;
 //   fc_radius_count / _fill      every point's neighbours within epsilon, at most K of them (the K nearest, ties to the
 //                                lower index), as (E,2) int64 [query, neighbour] rows grouped by query, neighbours ascending.
+//   fc_fps_batched, fc_radius_count_batched / _fill_batched      the same over a mini-batch of point sets (mesh b owns the rows
+//                                ptr[b] .. ptr[b+1] - 1 of pos): one FPS workgroup per mesh, and a radius search that looks for a
+//                                query's neighbours inside the query's own mesh only.
 // Both use one squared-distance formula, d2 = (dx*dx + dy*dy) + dz*dz with dx = p_n.x - p_q.x, each operation rounded on its
 // own (no contraction), so that numpy float32 evaluates exactly the same numbers.
 #include <hipcub/hipcub.hpp>
@@ -36,10 +39,9 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     return v;
 }
 
-// mind < 0 marks a selected point: fminf keeps it negative for good.
-__global__ __launch_bounds__(kFpsThreads) void fps_kernel(const float* __restrict__ pos, int N, int S, int start,
-                                                          int64_t* __restrict__ idx, float* __restrict__ mind_ws) {
-    __shared__ uint64_t slots[2][kFpsWaves];
+// One workgroup samples one point set.  mind < 0 marks a selected point: fminf keeps it negative for good.
+__device__ __forceinline__ void fps_body(const float* __restrict__ pos, int N, int S, int start, int64_t* __restrict__ idx,
+                                         float* __restrict__ mind_ws, uint64_t (*slots)[kFpsWaves]) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     float rx[kFpsRegPoints], ry[kFpsRegPoints], rz[kFpsRegPoints], rm[kFpsRegPoints];
 #pragma unroll
@@ -88,6 +90,33 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(const float* __restric
     }
 }
 
+__global__ __launch_bounds__(kFpsThreads) void fps_kernel(const float* __restrict__ pos, int N, int S, int start,
+                                                          int64_t* __restrict__ idx, float* __restrict__ mind_ws) {
+    __shared__ uint64_t slots[2][kFpsWaves];
+    fps_body(pos, N, S, start, idx, mind_ws, slots);
+}
+
+// ptr entry b clamped to [0, N]: a malformed table can give a meaningless result, never an access outside pos
+__device__ __forceinline__ int mesh_bound(const int64_t* __restrict__ ptr, int b, int N) {
+    const int64_t v = ptr[b];
+    return (int)(v < 0 ? 0 : (v > N ? N : v));
+}
+
+// Workgroup b samples mesh b: rows pos_ptr[b] .. pos_ptr[b+1] - 1 of pos, n_samples[b] of them from start[b], written to
+// idx[out_ptr[b] ..] as indices LOCAL to the mesh.  The workspace slice of a mesh starts at its first point.  Whatever the
+// tables hold, a mesh writes inside [0, S_total) and reads inside its own rows (a mesh whose samples do not fit is skipped).
+__global__ __launch_bounds__(kFpsThreads) void fps_batched_kernel(const float* __restrict__ pos, const int64_t* __restrict__ pos_ptr, int N,
+                                                                  const int64_t* __restrict__ n_samples, const int64_t* __restrict__ start,
+                                                                  const int64_t* __restrict__ out_ptr, int64_t S_total,
+                                                                  int64_t* __restrict__ idx, float* __restrict__ mind_ws) {
+    __shared__ uint64_t slots[2][kFpsWaves];
+    const int b = blockIdx.x;
+    const int p0 = mesh_bound(pos_ptr, b, N), n = max(mesh_bound(pos_ptr, b + 1, N), p0) - p0;
+    const int64_t S = n_samples[b], st = start[b], o = out_ptr[b];
+    if (n < 1 || S < 1 || S > n || st < 0 || st >= n || o < 0 || o > S_total - S) return;
+    fps_body(pos + 3 * (size_t)p0, n, (int)S, (int)st, idx + o, mind_ws + p0, slots);
+}
+
 // Stages candidates [tile, tile + kRadiusThreads) as float4 in LDS; the caller synchronises around it.
 __device__ __forceinline__ void stage_tile(float4* tile_pos, const float* __restrict__ pos, int tile, int N) {
     const int n = tile + threadIdx.x;
@@ -95,12 +124,8 @@ __device__ __forceinline__ void stage_tile(float4* tile_pos, const float* __rest
                                   : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// count[q] = min(#{n : d2(q,n) < r2}, K) as int64 (the scan input; count[N] = 0 so that the scan's last entry is the total),
-// overfull[q] = 1 when more than K points qualify.
-__global__ __launch_bounds__(kRadiusThreads) void radius_count_kernel(const float* __restrict__ pos, int N, float r2, int K,
-                                                                      int64_t* __restrict__ count, int32_t* __restrict__ overfull) {
-    __shared__ float4 tile_pos[kRadiusThreads];
-    const int q = blockIdx.x * kRadiusThreads + threadIdx.x;
+// #{n in [0,N) : d2(q,n) < r2} for the workgroup's queries (one per thread; every thread of the workgroup calls this)
+__device__ __forceinline__ int radius_count_body(float4* tile_pos, const float* __restrict__ pos, int N, int q, float r2) {
     const int qc = min(q, N - 1);
     const float qx = pos[3 * (size_t)qc], qy = pos[3 * (size_t)qc + 1], qz = pos[3 * (size_t)qc + 2];
     int c = 0;
@@ -114,6 +139,16 @@ __global__ __launch_bounds__(kRadiusThreads) void radius_count_kernel(const floa
             c += sq_dist(qx, qy, qz, p.x, p.y, p.z) < r2 ? 1 : 0;
         }
     }
+    return c;
+}
+
+// count[q] = min(#{n : d2(q,n) < r2}, K) as int64 (the scan input; count[N] = 0 so that the scan's last entry is the total),
+// overfull[q] = 1 when more than K points qualify.
+__global__ __launch_bounds__(kRadiusThreads) void radius_count_kernel(const float* __restrict__ pos, int N, float r2, int K,
+                                                                      int64_t* __restrict__ count, int32_t* __restrict__ overfull) {
+    __shared__ float4 tile_pos[kRadiusThreads];
+    const int q = blockIdx.x * kRadiusThreads + threadIdx.x;
+    const int c = radius_count_body(tile_pos, pos, N, q, r2);
     if (q < N) {
         count[q] = min(c, K);
         overfull[q] = c > K ? 1 : 0;
@@ -122,14 +157,11 @@ __global__ __launch_bounds__(kRadiusThreads) void radius_count_kernel(const floa
     }
 }
 
-// One wavefront per overfull query: the smallest t (a non-negative fp32 bit pattern) with #{d2 <= t} >= K, found by
-// bisection on the 31 magnitude bits, and the quota K - #{d2 < t} of candidates at exactly t that are kept (the lowest
-// indices).  Queries that are not overfull return at once.
-__global__ __launch_bounds__(256) void radius_select_kernel(const float* __restrict__ pos, int N, float r2, int K,
-                                                            const int32_t* __restrict__ overfull, uint32_t* __restrict__ thresh,
-                                                            int32_t* __restrict__ quota) {
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (q >= N || !overfull[q]) return;
+// One wavefront per overfull query q of the point set pos (N points): the smallest t (a non-negative fp32 bit pattern) with
+// #{d2 <= t} >= K, found by bisection on the 31 magnitude bits, and the quota K - #{d2 < t} of candidates at exactly t that
+// are kept (the lowest indices).
+__device__ __forceinline__ void radius_select_body(const float* __restrict__ pos, int N, int q, int lane, float r2, int K,
+                                                   uint32_t* __restrict__ thresh, int32_t* __restrict__ quota) {
     const float qx = pos[3 * (size_t)q], qy = pos[3 * (size_t)q + 1], qz = pos[3 * (size_t)q + 2];
     auto count_le = [&](uint32_t t) {          // #{n : bits(d2) <= t}, wave total
         int c = 0;
@@ -148,26 +180,35 @@ __global__ __launch_bounds__(256) void radius_select_kernel(const float* __restr
     }
     const int below = lo == 0 ? 0 : count_le(lo - 1);
     if (lane == 0) {
-        thresh[q] = lo;
-        quota[q] = K - below;
+        *thresh = lo;
+        *quota = K - below;
     }
 }
 
-// Same scan as the count kernel; each lane walks its candidates in index order and writes its row at its scanned offset.
-__global__ __launch_bounds__(kRadiusThreads) void radius_fill_kernel(const float* __restrict__ pos, int N, float r2, int64_t E,
-                                                                     const int64_t* __restrict__ offsets, const int32_t* __restrict__ overfull,
-                                                                     const uint32_t* __restrict__ thresh, const int32_t* __restrict__ quota,
-                                                                     int64_t* __restrict__ edges) {
-    __shared__ float4 tile_pos[kRadiusThreads];
-    const int q = blockIdx.x * kRadiusThreads + threadIdx.x;
+// Queries that are not overfull return at once.
+__global__ __launch_bounds__(256) void radius_select_kernel(const float* __restrict__ pos, int N, float r2, int K,
+                                                            const int32_t* __restrict__ overfull, uint32_t* __restrict__ thresh,
+                                                            int32_t* __restrict__ quota) {
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= N || !overfull[q]) return;
+    radius_select_body(pos, N, q, lane, r2, K, thresh + q, quota + q);
+}
+
+// Same scan as the count kernel over the point set pos (N points); each lane walks the candidates of its query q in index
+// order and writes its rows at its scanned offset.  Rows, and the per-query arrays, are numbered q + qbase / n + qbase.
+__device__ __forceinline__ void radius_fill_body(float4* tile_pos, const float* __restrict__ pos, int N, int q, int qbase, float r2,
+                                                 int64_t E, const int64_t* __restrict__ offsets, const int32_t* __restrict__ overfull,
+                                                 const uint32_t* __restrict__ thresh, const int32_t* __restrict__ quota,
+                                                 int64_t* __restrict__ edges) {
     const int qc = min(q, N - 1);
     const float qx = pos[3 * (size_t)qc], qy = pos[3 * (size_t)qc + 1], qz = pos[3 * (size_t)qc + 2];
-    const bool full = q < N && overfull[q];
-    const uint32_t t = full ? thresh[q] : 0xffffffffu;
-    int left_at_t = full ? quota[q] : 0;
+    const int qg = q + qbase;
+    const bool full = q < N && overfull[qg];
+    const uint32_t t = full ? thresh[qg] : 0xffffffffu;
+    int left_at_t = full ? quota[qg] : 0;
     // a non-overfull query keeps every d2 < r2: bits(d2) < 0xffffffff holds for all of them
-    int64_t out = q < N ? offsets[q] : 0;
-    const int64_t end = q < N ? min(offsets[q + 1], E) : 0;
+    int64_t out = q < N ? offsets[qg] : 0;
+    const int64_t end = q < N ? min(offsets[qg + 1], E) : 0;
     for (int tile = 0; tile < N; tile += kRadiusThreads) {
         __syncthreads();
         stage_tile(tile_pos, pos, tile, N);
@@ -183,13 +224,83 @@ __global__ __launch_bounds__(kRadiusThreads) void radius_fill_kernel(const float
                 keep = true;
                 --left_at_t;
             }
-            if (keep && out < end) {
-                edges[2 * out] = q;
-                edges[2 * out + 1] = tile + j;
+            if (keep && out >= 0 && out < end) {
+                edges[2 * out] = qg;
+                edges[2 * out + 1] = tile + j + qbase;
                 ++out;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(kRadiusThreads) void radius_fill_kernel(const float* __restrict__ pos, int N, float r2, int64_t E,
+                                                                     const int64_t* __restrict__ offsets, const int32_t* __restrict__ overfull,
+                                                                     const uint32_t* __restrict__ thresh, const int32_t* __restrict__ quota,
+                                                                     int64_t* __restrict__ edges) {
+    __shared__ float4 tile_pos[kRadiusThreads];
+    radius_fill_body(tile_pos, pos, N, blockIdx.x * kRadiusThreads + threadIdx.x, 0, r2, E, offsets, overfull, thresh, quota, edges);
+}
+
+// ---- the batched search: workgroups map to (mesh, query tile) pairs, so that the LDS candidate tile is always one mesh's.
+// Mesh b owns the workgroup slots base(b) .. base(b+1) - 1 with base(b) = ptr[b] / 256 + b (integer division): base is strictly
+// increasing and base(b+1) - base(b) = ptr[b+1]/256 - ptr[b]/256 + 1 >= ceil(n_b / 256), so N/256 + B workgroups suffice
+// whatever ptr holds, and a workgroup finds its mesh by bisection on base -- the prefix table in closed form, nothing to build
+// or to read back.  Slots past a mesh's last tile leave at once.  -> mesh rows [p0, p0 + n) and the tile's first local query.
+__device__ __forceinline__ bool mesh_tile(const int64_t* __restrict__ ptr, int B, int N, int g, int& p0, int& n, int& q0) {
+    int lo = 0, hi = B - 1;                                  // the largest b with base(b) <= g
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (mesh_bound(ptr, mid, N) / kRadiusThreads + mid <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    p0 = mesh_bound(ptr, lo, N);
+    n = max(mesh_bound(ptr, lo + 1, N), p0) - p0;
+    const long long first = (long long)(g - (p0 / kRadiusThreads + lo)) * kRadiusThreads;
+    q0 = (int)min(max(first, 0ll), (long long)n);
+    return first >= 0 && first < n;
+}
+
+__global__ __launch_bounds__(kRadiusThreads) void radius_count_batched_kernel(const float* __restrict__ pos, const int64_t* __restrict__ ptr,
+                                                                              int B, int N, float r2, int K, int64_t* __restrict__ count,
+                                                                              int32_t* __restrict__ overfull) {
+    __shared__ float4 tile_pos[kRadiusThreads];
+    if (blockIdx.x == 0 && threadIdx.x == 0) count[N] = 0;
+    int p0, n, q0;
+    if (!mesh_tile(ptr, B, N, blockIdx.x, p0, n, q0)) return;
+    const int q = q0 + threadIdx.x;
+    const int c = radius_count_body(tile_pos, pos + 3 * (size_t)p0, n, q, r2);
+    if (q < n) {
+        count[p0 + q] = min(c, K);
+        overfull[p0 + q] = c > K ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void radius_select_batched_kernel(const float* __restrict__ pos, const int64_t* __restrict__ ptr, int B,
+                                                                    int N, float r2, int K, const int32_t* __restrict__ overfull,
+                                                                    uint32_t* __restrict__ thresh, int32_t* __restrict__ quota) {
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= N || !overfull[q]) return;
+    int lo = 0, hi = B - 1;                                  // the mesh of q: the largest b with ptr[b] <= q
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (mesh_bound(ptr, mid, N) <= q) lo = mid;
+        else hi = mid - 1;
+    }
+    const int p0 = mesh_bound(ptr, lo, N), n = max(mesh_bound(ptr, lo + 1, N), p0) - p0;
+    if (q < p0 || q >= p0 + n) return;
+    radius_select_body(pos + 3 * (size_t)p0, n, q - p0, lane, r2, K, thresh + q, quota + q);
+}
+
+__global__ __launch_bounds__(kRadiusThreads) void radius_fill_batched_kernel(const float* __restrict__ pos, const int64_t* __restrict__ ptr,
+                                                                             int B, int N, float r2, int64_t E,
+                                                                             const int64_t* __restrict__ offsets,
+                                                                             const int32_t* __restrict__ overfull,
+                                                                             const uint32_t* __restrict__ thresh,
+                                                                             const int32_t* __restrict__ quota, int64_t* __restrict__ edges) {
+    __shared__ float4 tile_pos[kRadiusThreads];
+    int p0, n, q0;
+    if (!mesh_tile(ptr, B, N, blockIdx.x, p0, n, q0)) return;
+    radius_fill_body(tile_pos, pos + 3 * (size_t)p0, n, q0 + threadIdx.x, p0, r2, E, offsets, overfull, thresh, quota, edges);
 }
 
 }  // namespace fc
@@ -276,6 +387,61 @@ int fc_radius_fill(const float* pos, int32_t N, float epsilon, int32_t max_num_n
     char* w = static_cast<char*>(workspace);
     hipLaunchKernelGGL(fc::radius_fill_kernel, dim3((N + fc::kRadiusThreads - 1) / fc::kRadiusThreads), dim3(fc::kRadiusThreads), 0,
                        static_cast<hipStream_t>(stream), pos, N, epsilon * epsilon, E, reinterpret_cast<const int64_t*>(w + L.offsets),
+                       reinterpret_cast<const int32_t*>(w + L.overfull), reinterpret_cast<const uint32_t*>(w + L.thresh),
+                       reinterpret_cast<const int32_t*>(w + L.quota), supp_edges);
+    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+}
+
+size_t fc_fps_batched_workspace_bytes(int32_t N) { return fc_fps_workspace_bytes(N); }
+
+int fc_fps_batched(const float* pos, const int64_t* pos_ptr, int32_t N, int32_t B, const int64_t* n_samples, const int64_t* start,
+                   const int64_t* out_ptr, int64_t S_total, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pos || !pos_ptr || !n_samples || !start || !out_ptr || !idx || !workspace || N < 1 || B < 1 || S_total < 1 || S_total > N)
+        return FC_ERR_BAD_ARGUMENT;
+    if (workspace_bytes < fc_fps_batched_workspace_bytes(N)) return FC_ERR_WORKSPACE;
+    hipLaunchKernelGGL(fc::fps_batched_kernel, dim3((unsigned)B), dim3(fc::kFpsThreads), 0, static_cast<hipStream_t>(stream), pos, pos_ptr,
+                       N, n_samples, start, out_ptr, S_total, idx, static_cast<float*>(workspace));
+    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+}
+
+int fc_radius_count_batched(const float* pos, const int64_t* ptr, int32_t N, int32_t B, float epsilon, int32_t max_num_neighbors,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pos || !ptr || !workspace || N < 1 || B < 1 || !finite_positive(epsilon) || max_num_neighbors < 1 ||
+        (int64_t)N + (int64_t)fc::kRadiusThreads * B >= 2147483647LL)
+        return FC_ERR_BAD_ARGUMENT;
+    const RadiusLayout L(N);
+    if (workspace_bytes < L.total) return FC_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(workspace);
+    int64_t* count = reinterpret_cast<int64_t*>(w + L.count);
+    int64_t* offsets = reinterpret_cast<int64_t*>(w + L.offsets);
+    int32_t* overfull = reinterpret_cast<int32_t*>(w + L.overfull);
+    const float r2 = epsilon * epsilon;
+    const int K = max_num_neighbors;
+    // a query that no (mesh, tile) pair covers (a malformed ptr) counts nothing
+    if (hipMemsetAsync(count, 0, (size_t)N * 8, s) != hipSuccess || hipMemsetAsync(overfull, 0, (size_t)N * 4, s) != hipSuccess)
+        return FC_ERR_LAUNCH;
+    hipLaunchKernelGGL(fc::radius_count_batched_kernel, dim3((unsigned)(N / fc::kRadiusThreads + B)), dim3(fc::kRadiusThreads), 0, s, pos,
+                       ptr, B, N, r2, K, count, overfull);
+    hipLaunchKernelGGL(fc::radius_select_batched_kernel, dim3((N + 3) / 4), dim3(256), 0, s, pos, ptr, B, N, r2, K, overfull,
+                       reinterpret_cast<uint32_t*>(w + L.thresh), reinterpret_cast<int32_t*>(w + L.quota));
+    size_t scan_bytes = L.scan_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(w + L.scan, scan_bytes, count, offsets, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
+    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+}
+
+int fc_radius_fill_batched(const float* pos, const int64_t* ptr, int32_t N, int32_t B, float epsilon, int32_t max_num_neighbors, int64_t E,
+                           int64_t* supp_edges, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pos || !ptr || !workspace || N < 1 || B < 1 || !finite_positive(epsilon) || max_num_neighbors < 1 || E < 0 ||
+        (int64_t)N + (int64_t)fc::kRadiusThreads * B >= 2147483647LL)
+        return FC_ERR_BAD_ARGUMENT;
+    if (E > 0 && !supp_edges) return FC_ERR_BAD_ARGUMENT;
+    const RadiusLayout L(N);
+    if (workspace_bytes < L.total) return FC_ERR_WORKSPACE;
+    if (E == 0) return FC_OK;
+    char* w = static_cast<char*>(workspace);
+    hipLaunchKernelGGL(fc::radius_fill_batched_kernel, dim3((unsigned)(N / fc::kRadiusThreads + B)), dim3(fc::kRadiusThreads), 0,
+                       static_cast<hipStream_t>(stream), pos, ptr, B, N, epsilon * epsilon, E, reinterpret_cast<const int64_t*>(w + L.offsets),
                        reinterpret_cast<const int32_t*>(w + L.overfull), reinterpret_cast<const uint32_t*>(w + L.thresh),
                        reinterpret_cast<const int32_t*>(w + L.quota), supp_edges);
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;

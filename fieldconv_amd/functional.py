@@ -904,6 +904,9 @@ def soft_abs(x):
     return softAbs(x)
 
 
+from .pooling import mesh_mean, mesh_pool          # noqa: E402,F401  (per-mesh pooling over a MeshBatch: csrc/fc_segment.hip)
+
+
 def _tkey(t):
     return (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version, t.dtype)
 

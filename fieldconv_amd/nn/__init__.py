@@ -10,6 +10,7 @@ from .echo_block import ECHOBlock
 from .label_smoothing_loss import LabelSmoothingLoss
 from .twin_loss import TwinLoss
 from .twin_eval import TwinEval
+from .mesh_pool import MeshPool
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
-           'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval']
+           'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval', 'MeshPool']

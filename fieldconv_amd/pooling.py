@@ -1,0 +1,131 @@
+"""Per-mesh pooling over a mini-batch of meshes (csrc/fc_segment.hip): the functional forms and the autograd function under
+fieldconv_amd.nn.MeshPool and fieldconv_amd.functional.mesh_mean.
+
+A mini-batch is a disjoint union: mesh b owns the rows ptr[b] .. ptr[b+1] - 1 of every per-vertex tensor (ptr: (B+1,) int64,
+ascending, ptr[0] = 0, ptr[-1] = N; MeshBatch.ptr).  Features are (N,C) tensors on a ROCm device; there is no CPU or eager
+path: a CPU tensor raises.  ptr may live on the host or on the device.  Its VALUES are checked on the host before anything
+is launched: a host ptr costs nothing, a MeshBatch's ptr carries its host copy along, and any other device ptr is read back
+once -- the one synchronisation -- and remembered for as long as the tensor is not modified."""
+import ctypes
+
+import torch
+
+from . import _lib
+
+_DTYPES = {torch.float32: 0, torch.float64: 1, torch.complex64: 0, torch.complex128: 1}
+_REAL = {torch.complex64: torch.float32, torch.complex128: torch.float64}
+_REDUCE = {'mean': 0, 'sum': 1}
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def tag_ptr(ptr, host):
+    """Attach the host copy of a range table to its tensor (MeshBatch does, for the tables it builds from shapes)."""
+    ptr._fc_ptr_host = (ptr._version, [int(v) for v in host])
+    return ptr
+
+
+def ptr_host(ptr, what, name='ptr'):
+    """The entries of a (B+1,) int64 range table as Python ints, without a synchronisation where the tensor is on the host or
+    carries its host copy (tag_ptr); otherwise read back once and kept with the tensor."""
+    if not torch.is_tensor(ptr) or ptr.dim() != 1 or ptr.dtype != torch.int64 or ptr.numel() < 2:
+        raise ValueError(f'{what}: {name} must be a (B+1,) int64 tensor with B >= 1, got '
+                         f'{(tuple(ptr.shape), ptr.dtype) if torch.is_tensor(ptr) else type(ptr).__name__}')
+    memo = getattr(ptr, '_fc_ptr_host', None)
+    if memo is not None and memo[0] == ptr._version and len(memo[1]) == ptr.numel():
+        return memo[1]
+    host = ptr.tolist()
+    tag_ptr(ptr, host)
+    return host
+
+
+def check_ptr(ptr, n_rows, what, name='ptr'):
+    """-> the table's entries as Python ints; ValueError unless 0 = ptr[0] <= ptr[1] <= ... <= ptr[B] = n_rows."""
+    host = ptr_host(ptr, what, name)
+    if host[0] != 0 or host[-1] != n_rows:
+        raise ValueError(f'{what}: {name} must run from 0 to the number of rows ({n_rows}), got {name}[0] = {host[0]}, {name}[-1] = {host[-1]}')
+    if any(b < a for a, b in zip(host, host[1:])):
+        raise ValueError(f'{what}: {name} must be ascending (a mesh is a contiguous range of rows)')
+    return host
+
+
+def ptr_on(ptr, host, device):
+    """The table as a contiguous int64 tensor on `device` (its host copy travels with it)."""
+    if ptr.device == device and ptr.is_contiguous():
+        return ptr
+    return tag_ptr(ptr.to(device).contiguous(), host)
+
+
+class _MeshPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ptr, reduce, soft_abs):
+        lib = _lib.load()
+        xc = x.detach().contiguous()
+        N, C, B = int(xc.shape[0]), int(xc.shape[1]), int(ptr.numel()) - 1
+        dev, dt = xc.device, _DTYPES[xc.dtype]
+        rdt = _REAL[xc.dtype] if soft_abs else xc.dtype
+        with torch.cuda.device(dev):
+            nbytes = lib.fc_segment_pool_workspace_bytes(N, B, C, dt)
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            out = torch.empty((B, C), dtype=rdt, device=dev)
+            fn, name = (lib.fc_segment_pool_soft_abs_forward, 'fc_segment_pool_soft_abs_forward') if soft_abs else \
+                       (lib.fc_segment_pool_forward, 'fc_segment_pool_forward')
+            _lib.check(fn(_ptr(xc), _ptr(ptr), N, B, C, dt, reduce, _ptr(out), _ptr(ws), nbytes, _stream()), name)
+        ctx.save_for_backward(xc if soft_abs else None, ptr)
+        ctx.meta = (N, C, B, dt, reduce, soft_abs, xc.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, ptr = ctx.saved_tensors
+        N, C, B, dt, reduce, soft_abs, xdt = ctx.meta
+        dev = ptr.device
+        with torch.cuda.device(dev):
+            g = g.detach().to(_REAL[xdt] if soft_abs else xdt).contiguous()
+            gx = torch.empty((N, C), dtype=xdt, device=dev)
+            if soft_abs:
+                _lib.check(lib.fc_segment_pool_soft_abs_backward(_ptr(x), _ptr(g), _ptr(ptr), N, B, C, dt, reduce, _ptr(gx), _stream()),
+                           'fc_segment_pool_soft_abs_backward')
+            else:
+                _lib.check(lib.fc_segment_pool_backward(_ptr(g), _ptr(ptr), N, B, C, dt, reduce, _ptr(gx), _stream()),
+                           'fc_segment_pool_backward')
+        return gx, None, None, None
+
+
+def mesh_pool(x, ptr, reduce='mean', soft_abs=True, what='mesh_pool'):
+    """(B,C) real tensor: out[b,c] = mean (or sum) over the rows n of mesh b of softAbs(x[n,c]) for complex64 / complex128 x (N,C)
+    (soft_abs=True: |x| outside the origin box, 0 inside, reference utils/field.py:29-37 -- the classification read-out
+    mean(softAbs(x), dim=0) per mesh, |x| never written out), or of x[n,c] itself for float32 / float64 x (soft_abs=False).
+    An empty mesh gives 0.  Sums run in the input's precision in a fixed order (include/fieldconv_hip.h): the same bits on
+    every run.  Gradient flows to x."""
+    if reduce not in _REDUCE:
+        raise ValueError(f"{what}: reduce must be 'mean' or 'sum', got {reduce!r}")
+    want = (torch.complex64, torch.complex128) if soft_abs else (torch.float32, torch.float64)
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype not in want:
+        raise ValueError(f'{what}: x must be an (N,C) ' + ('complex64 or complex128' if soft_abs else 'float32 or float64') +
+                         f' tensor, got {(tuple(x.shape), x.dtype) if torch.is_tensor(x) else type(x).__name__}')
+    if not x.is_cuda:
+        raise RuntimeError(f'{what}: x is on {x.device}; fieldconv_amd pooling runs on a ROCm device and has no CPU path')
+    N, C = int(x.shape[0]), int(x.shape[1])
+    if C < 1 or C > 64 * 65535:
+        raise ValueError(f'{what}: between 1 and {64 * 65535} channels, got {C}')
+    host = check_ptr(ptr, N, what)
+    if N + 64 * (len(host) - 1) >= 2 ** 31 - 1:
+        raise ValueError(f'{what}: rows + 64 * meshes must stay below 2^31')
+    return _MeshPool.apply(x, ptr_on(ptr, host, x.device), _REDUCE[reduce], bool(soft_abs))
+
+
+def mesh_mean(values, ptr):
+    """(B,C): the mean over each mesh's rows of a real (N,C) float32 / float64 device tensor; (N,) input gives (B,).  With a
+    per-vertex loss this is the reference's batch_step arithmetic in one step:
+        mesh_mean(cross_entropy(logits, y, reduction='none')[:, None], batch.ptr).mean()  ==  sum_b CE_b / B"""
+    if torch.is_tensor(values) and values.dim() == 1:
+        return mesh_pool(values[:, None], ptr, 'mean', False, 'mesh_mean')[:, 0]
+    return mesh_pool(values, ptr, 'mean', False, 'mesh_mean')

@@ -570,6 +570,27 @@ const int64_t* fc_radius_edge_count_ptr(const void* workspace, int32_t N);
 int fc_radius_fill(const float* pos, int32_t N, float epsilon, int32_t max_num_neighbors, int64_t E, int64_t* supp_edges,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same over a mini-batch of point sets: pos (N,3) holds B sets one after the other, set b in the rows ptr[b] .. ptr[b+1] - 1
+ * (ptr: B+1 int64 in DEVICE memory, ascending, ptr[0] = 0, ptr[B] = N).  The tables live on the device and the library cannot
+ * look at them: the CALLER has checked them.  The kernels clamp what they read from them, so that a malformed table gives a
+ * meaningless result but no access outside the buffers.
+ * fps batched        one workgroup per set, fc_fps's rounds and selection rule inside it.  n_samples, start, out_ptr: B int64
+ *                    each, device memory; set b writes n_samples[b] indices LOCAL to the set (0 <= index < n_b, the first one
+ *                    start[b]) to idx[out_ptr[b] ..]; idx holds S_total int64.  A set with n_samples[b] outside [1, n_b], start[b]
+ *                    outside [0, n_b) or an output range outside idx writes nothing.  Workspace: the query below.
+ * radius batched     count / fill as above with neighbours searched inside the query's own set only; rows [q, n] are numbered in
+ *                    the union (local index + ptr[b]), queries ascending, each query's neighbours ascending: the single-set rows
+ *                    of every set plus its offset, one set after the other.  One epsilon and one K for the batch.  Workgroups
+ *                    map to (set, tile of 256 queries) pairs.  Workspace and edge count: fc_radius_workspace_bytes(N) and
+ *                    fc_radius_edge_count_ptr(workspace, N), as above.  N + 256 B < 2^31. */
+size_t fc_fps_batched_workspace_bytes(int32_t N);
+int fc_fps_batched(const float* pos, const int64_t* pos_ptr, int32_t N, int32_t B, const int64_t* n_samples, const int64_t* start,
+                   const int64_t* out_ptr, int64_t S_total, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
+int fc_radius_count_batched(const float* pos, const int64_t* ptr, int32_t N, int32_t B, float epsilon, int32_t max_num_neighbors,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int fc_radius_fill_batched(const float* pos, const int64_t* ptr, int32_t N, int32_t B, float epsilon, int32_t max_num_neighbors, int64_t E,
+                           int64_t* supp_edges, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- losses (the reference's TwinLoss, TwinEval, LabelSmoothingLoss) and the pair kernels under them ------------------ *
  * Features: xS (N_S,C) and xT (N_T,C), row-major, contiguous, device memory, real; dtype 0 = float32, 1 = float64 (every
  * device scalar and array of the call then has that type).  Pair lists: (K,2) int64 rows [row of xT, row of xS].
@@ -610,6 +631,32 @@ int fc_label_smoothing_forward(const void* pred, const int64_t* target, const vo
                                double confidence, double off_value, void* loss, void* workspace, size_t workspace_bytes, void* stream);
 int fc_label_smoothing_backward(const void* pred, const int64_t* target, const void* weight, const void* grad_loss, int64_t N, int32_t K,
                                 int32_t dtype, double confidence, double off_value, void* grad_pred, void* stream);
+
+
+/* ---- per-mesh pooling over a mini-batch of meshes (csrc/fc_segment.hip) ---------------------------------------------- *
+ * x (N,C) row-major, contiguous, device memory; mesh b owns the rows ptr[b] .. ptr[b+1] - 1 (ptr: B+1 int64 in DEVICE memory,
+ * ascending, ptr[0] = 0, ptr[B] = N, checked by the CALLER; the kernels clamp its entries to [0, N], so a malformed ptr
+ * gives meaningless values but no access outside the buffers).  dtype 0 = float32, 1 = float64; reduce 0 = mean, 1 = sum.
+ * soft abs forward   x: complex (interleaved re, im of that dtype); out[b,c] = reduce_{n in mesh b} softAbs(x[n,c]), out (B,C)
+ *                    real: |x| outside the origin box, 0 inside (reference utils/field.py:29-37), never written out per vertex.
+ * soft abs backward  grad_x[n,c] = grad_out[b,c] s_b x/|x| outside the origin box and 0 inside (fc_soft_abs_backward's rule),
+ *                    s_b = 1 (sum) or 1 / n_b (mean); grad_out (B,C) real, grad_x complex like x.
+ * forward, backward  the same for real x: out[b,c] = reduce x[n,c]; grad_x[n,c] = grad_out[b,c] s_b.
+ * An empty mesh gives 0 (also as a mean) and no gradient.  Sums run in the input's precision in an order fixed by (ptr, C):
+ * rows in chunks of 64 counted from the mesh's first row; in a chunk, four running sums over the rows w, w + 4, ... (w = 0..3,
+ * ascending), combined as (a_0 + a_1) + (a_2 + a_3); the chunks of a mesh the same way (chunks w, w + 4, ...; then
+ * (s_0 + s_1) + (s_2 + s_3)); a mean divides the sum by n_b.  No atomics: the same bits on every run.  Two launches forward,
+ * one backward.  N >= 0, B >= 1, 1 <= C <= 64 * 65535, N + 64 B < 2^31.  Workspace (forward only): the query below.
+ * No allocation or synchronisation inside. */
+size_t fc_segment_pool_workspace_bytes(int32_t N, int32_t B, int32_t C, int32_t dtype);
+int fc_segment_pool_soft_abs_forward(const void* x, const int64_t* ptr, int32_t N, int32_t B, int32_t C, int32_t dtype, int32_t reduce,
+                                     void* out, void* workspace, size_t workspace_bytes, void* stream);
+int fc_segment_pool_soft_abs_backward(const void* x, const void* grad_out, const int64_t* ptr, int32_t N, int32_t B, int32_t C,
+                                      int32_t dtype, int32_t reduce, void* grad_x, void* stream);
+int fc_segment_pool_forward(const void* x, const int64_t* ptr, int32_t N, int32_t B, int32_t C, int32_t dtype, int32_t reduce, void* out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int fc_segment_pool_backward(const void* grad_out, const int64_t* ptr, int32_t N, int32_t B, int32_t C, int32_t dtype, int32_t reduce,
+                             void* grad_x, void* stream);
 
 #ifdef __cplusplus
 }
