@@ -17,7 +17,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import FcEchoBlockParams, FcFilterParams, FcLiftBlockParams, FcMesh, FcResnetBlockParams, check
+from ._lib import FcEchoBlockParams, FcLiftBlockParams, FcMesh, FcResnetBlockParams, check
 from . import functional as Fn
 
 _NODES = None
@@ -64,28 +64,34 @@ def _graph_ref(nodes, graph, B):
     ref = graph._plans.get(key)
     if ref is None:
         empty = torch.empty(0, dtype=torch.int32, device=graph.rowptr_t.device)
-        if graph.geo_t is not None:
-            kind, fwd, bwd = 2, graph.geo_t, graph.rec_s
-        elif graph.factored:
-            kind, fwd, bwd = 1, graph.rec_t, graph.rec_s
-        else:
-            kind, fwd, bwd = 0, graph.sten_t, graph.sten_s
+        kind, fwd, bwd = Fn._records(graph)
         opt = lambda t: t if t is not None else empty
         ref = graph._plans[key] = nodes.GraphRef([graph.rowptr_t, opt(graph.nbr_t), opt(graph.runs_t), graph.rowptr_s, opt(graph.nbr_s),
                                                   opt(graph.runs_s), opt(fwd), opt(bwd)], graph.N, graph.E, graph.R, int(B), kind | (_lib.current_mode() << 8))
     return ref
 
 
-def _resnet_sizes(lib, graph, mesh, C_in, C_mid, C_out, B):
+def _resnet_sizes(graph, C_in, C_mid, C_out, B):
     """(saved bytes, forward workspace bytes, backward workspace bytes) of an FCResNetBlock on this mesh, cached with the graph"""
     key = ('resnet', C_in, C_mid, C_out, int(B))
     sizes = graph._plans.get(key)
     if sizes is None:
-        bp = FcResnetBlockParams(C_in, C_mid, C_out)
-        bref = ctypes.byref(bp)
+        lib, mesh, bref = _lib.load(), _mesh(graph, B), ctypes.byref(FcResnetBlockParams(C_in, C_mid, C_out))
         with Fn._on(graph.rowptr_t.device):      # (the plans follow the CU count of the device the launches will run on, not of the current one)
             sizes = graph._plans[key] = (lib.fc_resnet_block_saved_bytes(mesh.ref, bref), lib.fc_resnet_block_workspace_bytes(mesh.ref, bref, 0),
                                          lib.fc_resnet_block_workspace_bytes(mesh.ref, bref, 1))
+    return sizes
+
+
+def _echo_block_sizes(graph, C_in, n_des, n_bins, B):
+    """(saved bytes, forward workspace bytes, backward workspace bytes, descriptor length dS) of an ECHOBlock's tangent-feature half"""
+    key = ('echo_block', C_in, n_des, n_bins, int(B))
+    sizes = graph._plans.get(key)
+    if sizes is None:
+        lib, mesh, bref = _lib.load(), _mesh(graph, B), ctypes.byref(FcEchoBlockParams(C_in, n_des, n_bins))
+        with Fn._on(graph.rowptr_t.device):
+            sizes = graph._plans[key] = (lib.fc_echo_block_saved_bytes(mesh.ref, bref), lib.fc_echo_block_workspace_bytes(mesh.ref, bref, 0),
+                                         lib.fc_echo_block_workspace_bytes(mesh.ref, bref, 1), lib.fc_echo_hist_dim(n_bins))
     return sizes
 
 
@@ -94,8 +100,7 @@ def enabled():
     and while the benchmark brackets single kernels with events"""
     env = os.environ
     return (env.get('FIELDCONV_BLOCK_CALLS', '1') != '0' and Fn._ONE_CALL and env.get('FIELDCONV_NO_FUSED_EPILOGUE', '0') != '1'
-            and env.get('FIELDCONV_NO_EDGE_SPLIT', '0') != '1' and env.get('FC_SPLIT_FINISH', '0') in ('', '0')
-            and not Fn.kernel_timer.enabled)
+            and Fn._edge_split() and not Fn._split_finish() and not Fn.kernel_timer.enabled)
 
 
 def _plain_graph(graph):
@@ -110,14 +115,9 @@ class _Mesh:
     def __init__(self, graph, B):
         self.csr_t = Fn._csr(graph.rowptr_t, graph.nbr_t, graph.runs_t)
         self.csr_s = Fn._csr(graph.rowptr_s, graph.nbr_s, graph.runs_s)
-        if graph.geo_t is not None:
-            kind, fwd, bwd = 2, graph.geo_t, graph.rec_s
-        elif graph.factored:
-            kind, fwd, bwd = 1, graph.rec_t, graph.rec_s
-        else:
-            kind, fwd, bwd = 0, graph.sten_t, graph.sten_s
+        kind, fwd, bwd = Fn._records(graph)
         self.struct = FcMesh(graph.N, graph.E, graph.R, int(B), kind, ctypes.pointer(self.csr_t), ctypes.pointer(self.csr_s),
-                             fwd.data_ptr() if fwd is not None else None, bwd.data_ptr() if bwd is not None else None)
+                             Fn._dp(fwd), Fn._dp(bwd))
         self.ref = ctypes.byref(self.struct)
 
 
@@ -127,41 +127,6 @@ def _mesh(graph, B):
     if m is None:
         m = graph._plans[key] = _Mesh(graph, B)
     return m
-
-
-def _filter_params(conv_tensors, ftype, grads=None):
-    zonal, spherical, phase = conv_tensors
-    if grads is None:
-        return FcFilterParams(zonal.data_ptr(), spherical.data_ptr(), phase.data_ptr(), ftype, None, None, None)
-    return FcFilterParams(zonal.data_ptr(), spherical.data_ptr(), phase.data_ptr(), ftype, grads[0].data_ptr(), grads[1].data_ptr(),
-                          grads[2].data_ptr() if grads[2] is not None else None)
-
-
-def _carve_alloc(shapes, dev, zero=False):
-    """one flat float32 buffer and a view of it per shape (None entries stay None and take no room); pieces 16-byte aligned"""
-    sizes = []
-    for shp in shapes:
-        if shp is not None:
-            n = 1
-            for d in shp:
-                n *= d
-            sizes.append((n + 3) // 4 * 4)
-    flat = (torch.zeros if zero else torch.empty)(sum(sizes), dtype=torch.float32, device=dev)
-    parts = iter(flat.split(sizes))
-    out = []
-    for shp in shapes:
-        if shp is None:
-            out.append(None)
-        else:
-            n = 1
-            for d in shp:
-                n *= d
-            out.append(next(parts)[:n].view(shp) if n % 4 else next(parts).view(shp))
-    return out
-
-
-def _u8(nbytes, dev):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
 
 
 # ----------------------------------------------------------------------------------------------------------------- FCResNetBlock
@@ -177,14 +142,14 @@ class _ResnetBlockFn(torch.autograd.Function):
         z1, s1, p1, b1, z2, s2, p2, b2, re_w, im_w = tens
         C_mid, C_in, C_out = z1.shape[0], z1.shape[1], z2.shape[0]
         mesh = _mesh(graph, B)
-        bp = FcResnetBlockParams(C_in, C_mid, C_out, _filter_params((z1, s1, p1), ftype), _filter_params((z2, s2, p2), ftype),
+        bp = FcResnetBlockParams(C_in, C_mid, C_out, Fn._filter_params((z1, s1, p1, ftype)), Fn._filter_params((z2, s2, p2, ftype)),
                                  b1.data_ptr(), b2.data_ptr(), re_w.data_ptr(), im_w.data_ptr(), None, None, None, None)
-        sizes = _resnet_sizes(lib, graph, mesh, C_in, C_mid, C_out, B)
+        sizes = _resnet_sizes(graph, C_in, C_mid, C_out, B)
         dev = x.device
         with Fn._on(dev):
             out = torch.empty((graph.N, C_out), dtype=torch.complex64, device=dev)
-            saved = _u8(sizes[0], dev)
-            ws = _u8(sizes[1], dev)
+            saved = Fn._scratch(sizes[0], dev, 1)
+            ws = Fn._scratch(sizes[1], dev, 1)
             check(lib.fc_resnet_block_forward(Fn._p(x), mesh.ref, ctypes.byref(bp), Fn._p(out), Fn._p(saved), sizes[0], Fn._p(ws), sizes[1],
                                               Fn._stream()), 'fc_resnet_block_forward')
         ctx.save_for_backward(x, saved, *tens)
@@ -205,10 +170,10 @@ class _ResnetBlockFn(torch.autograd.Function):
                   b2.shape, re_w.shape, im_w.shape]
         with Fn._on(dev):
             gx = torch.empty_like(x)
-            g_z1, g_s1, g_p1, g_b1, g_z2, g_s2, g_p2, g_b2, g_re, g_im = _carve_alloc(shapes, dev)
-            ws = _u8(sizes[2], dev)
-            bp = FcResnetBlockParams(C_in, C_mid, C_out, _filter_params((z1, s1, p1), ftype, (g_z1, g_s1, g_p1)),
-                                     _filter_params((z2, s2, p2), ftype, (g_z2, g_s2, g_p2)), b1.data_ptr(), b2.data_ptr(),
+            g_z1, g_s1, g_p1, g_b1, g_z2, g_s2, g_p2, g_b2, g_re, g_im = Fn._carve(shapes, dev)
+            ws = Fn._scratch(sizes[2], dev, 1)
+            bp = FcResnetBlockParams(C_in, C_mid, C_out, Fn._filter_params((z1, s1, p1, ftype), (g_z1, g_s1, g_p1)),
+                                     Fn._filter_params((z2, s2, p2, ftype), (g_z2, g_s2, g_p2)), b1.data_ptr(), b2.data_ptr(),
                                      re_w.data_ptr(), im_w.data_ptr(), g_b1.data_ptr(), g_b2.data_ptr(), g_re.data_ptr(), g_im.data_ptr())
             check(lib.fc_resnet_block_backward(Fn._p(x), Fn._p(g_out), mesh.ref, ctypes.byref(bp), Fn._p(saved), sizes[0], Fn._p(gx), Fn._p(ws),
                                                sizes[2], Fn._stream()), 'fc_resnet_block_backward')
@@ -254,9 +219,7 @@ def resnet_block(block, x, graph):
     nodes = cpp_nodes()
     if nodes is not None:                      # the same node in C++ (csrc_torch/fc_torch_nodes.cpp): no interpreter in either pass
         B = int(c1.B)
-        sizes = graph._plans.get(('resnet', c1.in_channels, c1.out_channels, c2.out_channels, B))
-        if sizes is None:
-            sizes = _resnet_sizes(_lib.load(), graph, _mesh(graph, B), c1.in_channels, c1.out_channels, c2.out_channels, B)
+        sizes = _resnet_sizes(graph, c1.in_channels, c1.out_channels, c2.out_channels, B)
         return nodes.resnet_block(x, z1, s1, p1, mods['nonlin1']._parameters['bias'], z2, s2, p2, mods['nonlin2']._parameters['bias'],
                                   rp['Re'], rp['Im'], _graph_ref(nodes, graph, B), int(c1.ftype), sizes[0], sizes[1], sizes[2])
     return _ResnetBlockFn.apply(x, z1, s1, p1, mods['nonlin1']._parameters['bias'], z2, s2, p2, mods['nonlin2']._parameters['bias'],
@@ -275,19 +238,13 @@ class _EchoBlockFn(torch.autograd.Function):
         zonal, spherical, phase, bias = zonal.contiguous(), spherical.contiguous(), phase.contiguous(), bias.contiguous()
         C_in = zonal.shape[1]
         mesh = _mesh(graph, B)
-        bp = FcEchoBlockParams(C_in, n_des, n_bins, _filter_params((zonal, spherical, phase), ftype), bias.data_ptr(), None)
-        key = ('echo_block', C_in, n_des, n_bins, int(B))
-        sizes = graph._plans.get(key)
-        if sizes is None:
-            bref = ctypes.byref(bp)
-            with Fn._on(x.device):
-                sizes = graph._plans[key] = (lib.fc_echo_block_saved_bytes(mesh.ref, bref), lib.fc_echo_block_workspace_bytes(mesh.ref, bref, 0),
-                                             lib.fc_echo_block_workspace_bytes(mesh.ref, bref, 1), lib.fc_echo_hist_dim(n_bins))
+        bp = FcEchoBlockParams(C_in, n_des, n_bins, Fn._filter_params((zonal, spherical, phase, ftype)), bias.data_ptr(), None)
+        sizes = _echo_block_sizes(graph, C_in, n_des, n_bins, B)
         dev = x.device
         with Fn._on(dev):
             desc = torch.empty((graph.N, n_des, sizes[3]), dtype=torch.float32, device=dev)
-            saved = _u8(sizes[0], dev)
-            ws = _u8(sizes[1], dev)
+            saved = Fn._scratch(sizes[0], dev, 1)
+            ws = Fn._scratch(sizes[1], dev, 1)
             check(lib.fc_echo_block_forward(Fn._p(x), mesh.ref, Fn._p(slots[0]), Fn._p(slots[1]), ctypes.byref(bp), Fn._p(desc), Fn._p(saved),
                                             sizes[0], Fn._p(ws), sizes[1], Fn._stream()), 'fc_echo_block_forward')
         ctx.save_for_backward(x, saved, zonal, spherical, phase, bias)
@@ -306,9 +263,9 @@ class _EchoBlockFn(torch.autograd.Function):
         with Fn._on(dev):
             gx = torch.empty_like(x)
             # the module's bias has in_channels entries of which the first n_des act (reference nn/echo_block.py:57,93): the rest get zero
-            g_z, g_s, g_p, g_b = _carve_alloc(shapes, dev, zero=bias.numel() > ctx.n_des)
-            ws = _u8(sizes[2], dev)
-            bp = FcEchoBlockParams(zonal.shape[1], ctx.n_des, ctx.n_bins, _filter_params((zonal, spherical, phase), ftype, (g_z, g_s, g_p)),
+            g_z, g_s, g_p, g_b = Fn._carve(shapes, dev, zero=bias.numel() > ctx.n_des)
+            ws = Fn._scratch(sizes[2], dev, 1)
+            bp = FcEchoBlockParams(zonal.shape[1], ctx.n_des, ctx.n_bins, Fn._filter_params((zonal, spherical, phase, ftype), (g_z, g_s, g_p)),
                                    bias.data_ptr(), g_b.data_ptr())
             check(lib.fc_echo_block_backward(Fn._p(x), Fn._p(g_desc), mesh.ref, Fn._p(slots[2]), Fn._p(slots[3]), ctypes.byref(bp), Fn._p(saved),
                                              sizes[0], Fn._p(gx), Fn._p(ws), sizes[2], Fn._stream()), 'fc_echo_block_backward')
@@ -327,14 +284,8 @@ def echo_block_descriptors(block, x, graph, ln, wxp):
     slots = Fn.echo_slot_order(graph, ln, wxp)
     nodes = cpp_nodes()
     if nodes is not None:
-        lib, B = _lib.load(), int(conv.B)
-        key = ('echo_block', conv.in_channels, int(n_des), n_bins, B)
-        sizes = graph._plans.get(key)
-        if sizes is None:
-            bref = ctypes.byref(FcEchoBlockParams(conv.in_channels, int(n_des), n_bins))
-            mesh = _mesh(graph, B)
-            sizes = graph._plans[key] = (lib.fc_echo_block_saved_bytes(mesh.ref, bref), lib.fc_echo_block_workspace_bytes(mesh.ref, bref, 0),
-                                         lib.fc_echo_block_workspace_bytes(mesh.ref, bref, 1), lib.fc_echo_hist_dim(n_bins))
+        B = int(conv.B)
+        sizes = _echo_block_sizes(graph, conv.in_channels, int(n_des), n_bins, B)
         z, sp, ph = _conv_tensors(conv)
         return nodes.echo_block(x, z, sp, ph, block._modules['nonlin']._parameters['bias'], _graph_ref(nodes, graph, B), list(slots[:4]),
                                 int(conv.ftype), int(n_des), n_bins, sizes[3], sizes[0], sizes[1], sizes[2])
@@ -427,23 +378,14 @@ class _EchoHeadFn(torch.autograd.Function):
             hp = _lib.FcEchoHeadParams(D, H1, H2, C, Q, w1.data_ptr(), None, w2.data_ptr(), None, w3.data_ptr(), None, wr.data_ptr(), None,
                                        None, None, None, None, None, None, None, None)
             nws = lib.fc_echo_head_backward_workspace_bytes(N, ctypes.byref(hp))
-
-            def carve(sizes, extra=0):
-                buf = torch.empty(sum(-(-s // 4) * 4 for s in sizes) + extra, dtype=torch.float32, device=x.device)
-                parts, off = [], 0
-                for s in sizes:
-                    parts.append(buf[off:off + s])
-                    off += -(-s // 4) * 4
-                return parts, buf[off:]
             # the parameter gradients in a buffer of their own (they may live on as .grad); the flowing gradients and scratch in another
-            (g_w1, g_b1, g_w2, g_b2, g_w3, g_b3, g_wr, g_br), _ = carve([H1 * D, H1, H2 * H1, H2, Q * H2, Q, Q * C, Q])
-            (g_d, gx, g_h1), ws = carve([N * D, 2 * N * C, N * H1], (nws + 3) // 4)
+            g_w1, g_b1, g_w2, g_b2, g_w3, g_b3, g_wr, g_br = Fn._carve([(H1, D), (H1,), (H2, H1), (H2,), (Q, H2), (Q,), (Q, C), (Q,)], x.device)
+            g_d, gx, g_h1, ws = Fn._carve([(N, D), (N, C, 2), (N, H1)], x.device, extra=(nws + 3) // 4)
             hp.g_w1, hp.g_b1, hp.g_w2, hp.g_b2 = g_w1.data_ptr(), g_b1.data_ptr(), g_w2.data_ptr(), g_b2.data_ptr()
             hp.g_w3, hp.g_b3, hp.g_wr, hp.g_br = g_w3.data_ptr(), g_b3.data_ptr(), g_wr.data_ptr(), g_br.data_ptr()
             check(lib.fc_echo_head_backward(Fn._p(d), Fn._p(x), Fn._p(h1), Fn._p(h2), Fn._p(g), ctypes.byref(hp), Fn._p(g_d), Fn._p(gx),
                                             Fn._p(g_h1), Fn._p(ws), nws, N, Fn._stream()), 'fc_echo_head_backward')
-        return (g_d.view(N, D), torch.view_as_complex(gx.view(N, C, 2)), g_w1.view(H1, D), g_b1, g_w2.view(H2, H1), g_b2, g_w3.view(Q, H2), g_b3,
-                g_wr.view(Q, C), g_br)
+        return g_d, torch.view_as_complex(gx), g_w1, g_b1, g_w2, g_b2, g_w3, g_b3, g_wr, g_br
 
 
 def echo_block_tail(block, d, x):
@@ -480,7 +422,7 @@ class _LiftBlockFn(torch.autograd.Function):
         zonal_ang, zonal_mag, phase, bias = zonal_ang.contiguous(), zonal_mag.contiguous(), phase.contiguous(), bias.contiguous()
         N, C_in = x.shape
         C_out, _, R = zonal_ang.shape
-        by_t, by_s = Fn._csr(csr.rowptr_t, csr.nbr_t, None), Fn._csr(csr.rowptr_s, csr.nbr_s, None)
+        by_t, by_s = Fn._by_target(csr), Fn._by_source(csr)
         mesh = FcMesh(N, csr.E, R, 0, 0, ctypes.pointer(by_t), ctypes.pointer(by_s), None, None)
         bp = FcLiftBlockParams(C_in, C_out, ftype, zonal_ang.data_ptr(), zonal_mag.data_ptr(), phase.data_ptr(), bias.data_ptr(),
                                None, None, None, None)
@@ -488,7 +430,7 @@ class _LiftBlockFn(torch.autograd.Function):
         dev = x.device
         with Fn._on(dev):
             out = torch.empty((N, C_out), dtype=torch.complex64, device=dev)
-            saved = _u8(nsaved, dev)
+            saved = Fn._scratch(nsaved, dev, 1)
             check(lib.fc_lift_block_forward(Fn._p(x), Fn._p(sten), stride, ctypes.byref(mesh), Fn._p(csr.perm_t), ctypes.byref(bp), Fn._p(out),
                                             Fn._p(saved), nsaved, Fn._stream()), 'fc_lift_block_forward')
         ctx.save_for_backward(sten, saved, zonal_ang, zonal_mag, phase, bias)
@@ -502,17 +444,17 @@ class _LiftBlockFn(torch.autograd.Function):
         csr, ftype = ctx.csr, ctx.ftype
         N, C_in, C_out, R = ctx.dims
         g_out = g_out.contiguous()
-        by_t, by_s = Fn._csr(csr.rowptr_t, csr.nbr_t, None), Fn._csr(csr.rowptr_s, csr.nbr_s, None)
+        by_t, by_s = Fn._by_target(csr), Fn._by_source(csr)
         mesh = FcMesh(N, csr.E, R, 0, 0, ctypes.pointer(by_t), ctypes.pointer(by_s), None, None)
         dev = g_out.device
         shapes = [zonal_ang.shape, zonal_mag.shape, phase.shape if ftype != 0 else None, bias.shape]
         with Fn._on(dev):
             gx = torch.empty((N, C_in), dtype=torch.float32, device=dev)
-            g_za, g_zm, g_ph, g_b = _carve_alloc(shapes, dev)
+            g_za, g_zm, g_ph, g_b = Fn._carve(shapes, dev)
             bp = FcLiftBlockParams(C_in, C_out, ftype, zonal_ang.data_ptr(), zonal_mag.data_ptr(), phase.data_ptr(), bias.data_ptr(),
-                                   g_za.data_ptr(), g_zm.data_ptr(), g_ph.data_ptr() if g_ph is not None else None, g_b.data_ptr())
+                                   g_za.data_ptr(), g_zm.data_ptr(), Fn._dp(g_ph), g_b.data_ptr())
             nws = lib.fc_lift_block_workspace_bytes(ctypes.byref(mesh), ctypes.byref(bp), 1)
-            ws = _u8(nws, dev)
+            ws = Fn._scratch(nws, dev, 1)
             check(lib.fc_lift_block_backward(Fn._p(g_out), Fn._p(sten), ctx.stride, ctypes.byref(mesh), Fn._p(csr.perm_s), ctypes.byref(bp),
                                              Fn._p(saved), ctx.nsaved, Fn._p(gx), Fn._p(ws), nws, Fn._stream()), 'fc_lift_block_backward')
         return gx, None, None, g_za, g_zm, g_ph, g_b, None, None

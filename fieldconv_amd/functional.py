@@ -4,6 +4,7 @@ The tensors are plain torch device buffers; only raw pointers, sizes and the cur
 cross into libfieldconv_hip.so (include/fieldconv_hip.h).
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -113,8 +114,96 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _dp(t):
+    """data pointer of an optional tensor (None: NULL) for a struct field"""
+    return t.data_ptr() if t is not None else None
+
+
+def _po(t):
+    """_p of an optional tensor (None: NULL)"""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
 def _csr(rowptr, nbr, runs=None):
-    return FcCsr(rowptr.data_ptr(), nbr.data_ptr() if nbr.numel() else None, runs.data_ptr() if runs is not None else None)
+    return FcCsr(rowptr.data_ptr(), nbr.data_ptr() if nbr.numel() else None, _dp(runs))
+
+
+def _by_target(csr):
+    """the by-target grouping of an edge grouping without ring runs (run-time kernels, ECHO, TransField)"""
+    return _csr(csr.rowptr_t, csr.nbr_t, None)
+
+
+def _by_source(csr):
+    return _csr(csr.rowptr_s, csr.nbr_s, None)
+
+
+def _records(graph):
+    """(record kind, forward records, backward records) of a support graph: 2 geometric-phase records, 1 factored records, 0 dense
+    stencil rows (include/fieldconv_hip.h: fc_mesh.kind); the backward pass reads factored records for both record kinds"""
+    if graph.geo_t is not None:
+        return 2, graph.geo_t, graph.rec_s
+    if graph.factored:
+        return 1, graph.rec_t, graph.rec_s
+    return 0, graph.sten_t, graph.sten_s
+
+
+def _scratch(nbytes, device, floor=0):
+    """Device scratch of `nbytes` bytes (uint8), the ONE place workspaces are allocated.  What a zero-byte request gives follows the
+    entry point: floor=0 an empty tensor (its pointer is NULL), floor=1 a live one-byte buffer (the block-level entry points),
+    floor=None no tensor at all (fc_forward_*, fc_cgemm: _po(None) is NULL)."""
+    if floor is None:
+        if not nbytes:
+            return None
+        floor = 0
+    return torch.empty(max(int(nbytes), floor), dtype=torch.uint8, device=device)
+
+
+def _carve(shapes, device, zero=False, extra=None):
+    """One flat float32 buffer and a view of it per shape, pieces 16-byte aligned (None entries stay None and take no room); with
+    `extra`, that many floats behind the pieces come last, flat.  Everything returned shares ONE storage."""
+    counts = [math.prod(shp) for shp in shapes if shp is not None]
+    sizes = [(n + 3) // 4 * 4 for n in counts]
+    flat = (torch.zeros if zero else torch.empty)(sum(sizes) + (extra or 0), dtype=torch.float32, device=device)
+    parts = iter(flat.split(sizes if extra is None else sizes + [extra]))
+    counts = iter(counts)
+    out = []
+    for shp in shapes:
+        if shp is None:
+            out.append(None)
+        else:
+            n = next(counts)
+            out.append(next(parts)[:n].view(shp) if n % 4 else next(parts).view(shp))
+    if extra is not None:
+        out.append(next(parts))
+    return out
+
+
+def _edge_split():
+    """False under FIELDCONV_NO_EDGE_SPLIT=1 (development: no workgroups sharing a tile; read per call, tests flip it)"""
+    return os.environ.get('FIELDCONV_NO_EDGE_SPLIT', '0') != '1'
+
+
+def _split_finish():
+    """True under FC_SPLIT_FINISH (the development library's two-kernel finish, which hands gW_eff from one kernel to the other)"""
+    return os.environ.get('FC_SPLIT_FINISH', '0') not in ('', '0')
+
+
+def _epilogue(addend, bias, act):
+    """fc_epilogue of a forward launch -- residual addend, modReLU bias, where the activated rows go -- or None without either"""
+    if addend is None and bias is None:
+        return None
+    return FcEpilogue(_dp(addend), _dp(bias), _dp(act))
+
+
+def _filter_params(params, grads=None, bias_sum=None):
+    """fc_filter_params of params = (zonal, spherical, phase, ftype); grads = (g_zonal, g_spherical, g_phase or None): where the
+    backward pass leaves their gradients; bias_sum = (partials, n_parts, g_bias): the rider of the finishing launch"""
+    zonal, spherical, phase, ftype = params
+    g_z, g_s, g_p = grads if grads is not None else (None, None, None)
+    fp = FcFilterParams(zonal.data_ptr(), spherical.data_ptr(), phase.data_ptr(), ftype, _dp(g_z), _dp(g_s), _dp(g_p))
+    if bias_sum is not None:
+        fp.bias_partials, fp.bias_nparts, fp.g_bias = bias_sum[0].data_ptr(), bias_sum[1], bias_sum[2].data_ptr()
+    return fp
 
 
 def make_dims(graph, I, O, B):
@@ -141,7 +230,7 @@ class _FieldConvFn(torch.autograd.Function):
             st = _stream()
 
             def pack(pl, wpk_f, wpk_b):
-                check(lib.fc_pack_filter(_p(w_eff), _p(wpk_f), _p(wpk_b) if wpk_b is not None else None, pl.dref, pl.records, st), 'fc_pack_filter')
+                check(lib.fc_pack_filter(_p(w_eff), _p(wpk_f), _po(wpk_b), pl.dref, pl.records, st), 'fc_pack_filter')
             y, wpk_b = _run_forward(lib, x, graph, plan, O, st, pack)
         ctx.save_for_backward(x, wpk_b)
         ctx.graph = graph
@@ -184,7 +273,7 @@ def _conv_plan(lib, graph, I, O, B):
     plan.n_bwd = lib.fc_packed_filter_floats_bwd(plan.dref, plan.records)
     plan.ws_bwd = lib.fc_backward_workspace_bytes(plan.dref, plan.records)
     plan.ws_fwd = 0
-    if graph.factored and os.environ.get('FIELDCONV_NO_EDGE_SPLIT', '0') != '1':
+    if graph.factored and _edge_split():
         plan.ws_fwd = lib.fc_forward_workspace_bytes(plan.dref)      # non-zero on small meshes with wide supports
     plan.csr_t = _csr(graph.rowptr_t, graph.nbr_t, graph.runs_t)
     plan.csr_s = _csr(graph.rowptr_s, graph.nbr_s, graph.runs_s)
@@ -193,10 +282,9 @@ def _conv_plan(lib, graph, I, O, B):
     return plan
 
 
-def _launch_forward(lib, x, graph, wpk_f, plan, O, st, addend=None, bias=None, out=None, row0=0):
-    """-> y, or (pre-activation, activated) when a modReLU bias is given: the residual `addend` and the modReLU run in the
-    kernel's epilogue (include/fieldconv_hip.h: fc_epilogue).  `plan` may cover the targets [row0, row0 + plan.dims.N) only
-    (_row_plan); the rows then land in the tensors of `out` = (y, activated)."""
+def _forward_buffers(x, plan, O, addend, bias, out=None, row0=0):
+    """What a forward launch of `plan` writes and needs -> (y, activated or None, reference to its fc_epilogue or None, workspace or
+    None).  `out` = (y, activated) of the whole mesh: the launch covers the rows [row0, row0 + plan.dims.N) of them."""
     n = plan.dims.N
     if out is None:
         y = torch.empty((n, O), dtype=torch.complex64, device=x.device)
@@ -204,22 +292,22 @@ def _launch_forward(lib, x, graph, wpk_f, plan, O, st, addend=None, bias=None, o
     else:
         y, act = out[0][row0:row0 + n], (out[1][row0:row0 + n] if out[1] is not None else None)
         addend = addend[row0:row0 + n] if addend is not None else None
-    epi = None
-    if addend is not None or bias is not None:
-        epi = ctypes.byref(FcEpilogue(addend.data_ptr() if addend is not None else None, bias.data_ptr() if bias is not None else None,
-                                      act.data_ptr() if act is not None else None))
-    nbytes = plan.ws_fwd
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    wsp = _p(ws) if ws is not None else None
+    epi = _epilogue(addend, bias, act)
+    return y, act, (ctypes.byref(epi) if epi is not None else None), _scratch(plan.ws_fwd, x.device, None)
+
+
+def _launch_forward(lib, x, graph, wpk_f, plan, O, st, addend=None, bias=None, out=None, row0=0):
+    """-> y, or (pre-activation, activated) when a modReLU bias is given: the residual `addend` and the modReLU run in the
+    kernel's epilogue (include/fieldconv_hip.h: fc_epilogue).  `plan` may cover the targets [row0, row0 + plan.dims.N) only
+    (_row_plan); the rows then land in the tensors of `out` = (y, activated)."""
+    y, act, epi, ws = _forward_buffers(x, plan, O, addend, bias, out, row0)
+    kind, recs, _ = _records(graph)
     with _timed('fc_forward'):
-        if graph.geo_t is not None:
-            check(lib.fc_forward_geometric(_p(x), _p(graph.geo_t), plan.cref_t, _p(wpk_f), _p(y), wsp, nbytes, plan.dref, epi, st),
-                  'fc_forward_geometric')
-        elif graph.factored:
-            check(lib.fc_forward_factored(_p(x), _p(graph.rec_t), plan.cref_t, _p(wpk_f), _p(y), wsp, nbytes, plan.dref, epi, st),
-                  'fc_forward_factored')
+        if kind == 0:
+            check(lib.fc_forward(_p(x), _p(recs), plan.cref_t, _p(wpk_f), _p(y), plan.dref, epi, st), 'fc_forward')
         else:
-            check(lib.fc_forward(_p(x), _p(graph.sten_t), plan.cref_t, _p(wpk_f), _p(y), plan.dref, epi, st), 'fc_forward')
+            name = 'fc_forward_geometric' if kind == 2 else 'fc_forward_factored'
+            check(getattr(lib, name)(_p(x), _p(recs), plan.cref_t, _p(wpk_f), _p(y), _po(ws), plan.ws_fwd, plan.dref, epi, st), name)
     return y if bias is None else (y, act)
 
 
@@ -240,7 +328,7 @@ def _row_plan(lib, graph, whole, row0, nrows):
     plan.n_bwd = whole.n_bwd
     plan.ws_bwd = whole.ws_bwd
     plan.ws_fwd = 0
-    if os.environ.get('FIELDCONV_NO_EDGE_SPLIT', '0') != '1':
+    if _edge_split():
         plan.ws_fwd = lib.fc_forward_workspace_bytes(plan.dref)
     plan.csr_t = _csr(graph.rowptr_t[row0:], graph.nbr_t, graph.runs_t[row0:] if graph.runs_t is not None else None)
     plan.csr_s, plan.cref_s = whole.csr_s, whole.cref_s
@@ -268,19 +356,10 @@ def _run_forward(lib, x, graph, plan, O, st, pack, addend=None, bias=None, param
         wpk_f = torch.empty(plan.n_fwd, dtype=torch.float32, device=dev)
         if params is not None and between is None and _ONE_CALL and not kernel_timer.enabled:
             # filter images + forward launch in one foreign call (fc_forward_params)
-            zonal, spherical, phase, ftype = params
-            y = torch.empty((graph.N, O), dtype=torch.complex64, device=dev)
-            act = torch.empty_like(y) if bias is not None else None
-            epi = None
-            if addend is not None or bias is not None:
-                epi = ctypes.byref(FcEpilogue(addend.data_ptr() if addend is not None else None,
-                                              bias.data_ptr() if bias is not None else None, act.data_ptr() if act is not None else None))
-            fp = FcFilterParams(zonal.data_ptr(), spherical.data_ptr(), phase.data_ptr(), ftype, None, None, None)
-            nbytes = plan.ws_fwd
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-            kind, recs = (2, graph.geo_t) if graph.geo_t is not None else ((1, graph.rec_t) if graph.factored else (0, graph.sten_t))
-            check(lib.fc_forward_params(_p(x), _p(recs), plan.cref_t, kind, ctypes.byref(fp), _p(wpk_f), _p(wpk_b), _p(y),
-                                        _p(ws) if ws is not None else None, nbytes, plan.dref, plan.records, epi, st), 'fc_forward_params')
+            y, act, epi, ws = _forward_buffers(x, plan, O, addend, bias)
+            kind, recs, _ = _records(graph)
+            check(lib.fc_forward_params(_p(x), _p(recs), plan.cref_t, kind, ctypes.byref(_filter_params(params)), _p(wpk_f), _p(wpk_b), _p(y),
+                                        _po(ws), plan.ws_fwd, plan.dref, plan.records, epi, st), 'fc_forward_params')
             return (y if bias is None else (y, act)), wpk_b
         pack(plan, wpk_f, wpk_b)
         if between is not None:
@@ -300,6 +379,12 @@ def _run_forward(lib, x, graph, plan, O, st, pack, addend=None, bias=None, param
     return (y if bias is None else (y, act)), wpk_b
 
 
+def _param_grads(params):
+    """uninitialised gradients of params = (zonal, spherical, phase, ftype); the phase offsets are parameters for ftype 1 only"""
+    zonal, spherical, phase, ftype = params
+    return torch.empty_like(zonal), torch.empty_like(spherical), (torch.empty_like(phase) if ftype == 1 else None)
+
+
 def _launch_backward(lib, x, gy, graph, wpk_b, plan, wshape, st, params=None, bias_sum=None):
     """-> (gx, gw_eff, parameter gradients or None).  params = (zonal, spherical, phase, ftype): also the VJP of the filter
     assembly.  One foreign call for the whole pass (fc_backward_all) unless something has to happen between the kernels: a
@@ -309,25 +394,18 @@ def _launch_backward(lib, x, gy, graph, wpk_b, plan, wshape, st, params=None, bi
     O, I, R, F = wshape
     gx = torch.empty_like(x)
     # with module parameters only their gradients are wanted: the (O,I,R,F) tensor is never written (gw_eff = NULL)
-    # (the development library's two-kernel finish, FC_SPLIT_FINISH=1, hands gW_eff from one kernel to the other)
-    want_gw = params is None or KEEP_GW_EFF or os.environ.get('FC_SPLIT_FINISH', '0') not in ('', '0')
+    # (or under the development library's two-kernel finish)
+    want_gw = params is None or KEEP_GW_EFF or _split_finish()
     gw = torch.empty((O, I, R, F), dtype=torch.complex64, device=x.device) if want_gw else None
     nbytes = plan.ws_bwd
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    sten = graph.rec_s if graph.factored else graph.sten_s
+    ws = _scratch(nbytes, x.device)
     wsp = _p(ws)
+    sten = _records(graph)[2]
     pgrads = fp = None
     if params is not None:
-        zonal, spherical, phase, ftype = params
-        g_z = torch.empty_like(zonal)
-        g_s = torch.empty_like(spherical)
-        g_p = torch.empty_like(phase) if ftype == 1 else None
-        pgrads = (g_z, g_s, g_p)
-        fp = FcFilterParams(zonal.data_ptr(), spherical.data_ptr(), phase.data_ptr(), ftype, g_z.data_ptr(), g_s.data_ptr(),
-                            g_p.data_ptr() if g_p is not None else None)
-        if bias_sum is not None:
-            fp.bias_partials, fp.bias_nparts, fp.g_bias = bias_sum[0].data_ptr(), bias_sum[1], bias_sum[2].data_ptr()
-    gwp = _p(gw) if gw is not None else None
+        pgrads = _param_grads(params)
+        fp = _filter_params(params, pgrads, bias_sum)
+    gwp = _po(gw)
     if graph.on_gx is None and _ONE_CALL and not kernel_timer.enabled:
         check(lib.fc_backward_all(_p(x), _p(gy), _p(sten), plan.cref_s, plan.records, _p(wpk_b), _p(gx), gwp,
                                   ctypes.byref(fp) if fp is not None else None, wsp, nbytes, plan.dref, st), 'fc_backward_all')
@@ -361,6 +439,16 @@ def _launch_backward(lib, x, gy, graph, wpk_b, plan, wshape, st, params=None, bi
     return gx, gw, pgrads
 
 
+def _param_packer(lib, params, st):
+    """the pack(plan, wpk_f, wpk_b) of _run_forward for module parameters (zonal, spherical, phase, ftype): fc_pack_filter_params"""
+    zonal, spherical, phase, ftype = params
+
+    def pack(pl, wpk_f, wpk_b):
+        check(lib.fc_pack_filter_params(_p(zonal), _p(spherical), _p(phase), ftype, _p(wpk_f), _po(wpk_b), pl.dref, pl.records, st),
+              'fc_pack_filter_params')
+    return pack
+
+
 @_lib.keep_mode
 class _FieldConvParamFn(torch.autograd.Function):
     """FieldConv straight from the module parameters: the filter assembly of reference
@@ -377,11 +465,8 @@ class _FieldConvParamFn(torch.autograd.Function):
         plan = _conv_plan(lib, graph, I, O, B)
         with _on(x.device):
             st = _stream()
-
-            def pack(pl, wpk_f, wpk_b):
-                check(lib.fc_pack_filter_params(_p(zonal), _p(spherical), _p(phase), ftype, _p(wpk_f), _p(wpk_b) if wpk_b is not None else None, pl.dref,
-                                                pl.records, st), 'fc_pack_filter_params')
-            y, wpk_b = _run_forward(lib, x, graph, plan, O, st, pack, params=(zonal, spherical, phase, ftype))
+            params = (zonal, spherical, phase, ftype)
+            y, wpk_b = _run_forward(lib, x, graph, plan, O, st, _param_packer(lib, params, st), params=params)
         ctx.save_for_backward(x, wpk_b, zonal, spherical, phase)
         ctx.graph, ctx.ftype, ctx.wshape = graph, ftype, (O, I, R, F)
         return y
@@ -418,11 +503,8 @@ class _FieldConvActFn(torch.autograd.Function):
         plan = _conv_plan(lib, graph, I, O, B)
         with _on(x.device):
             st = _stream()
-            def pack(pl, wpk_f, wpk_b):
-                check(lib.fc_pack_filter_params(_p(zonal), _p(spherical), _p(phase), ftype, _p(wpk_f), _p(wpk_b) if wpk_b is not None else None, pl.dref,
-                                                pl.records, st), 'fc_pack_filter_params')
-            (pre, act), wpk_b = _run_forward(lib, x, graph, plan, O, st, pack, addend=addend, bias=bias,
-                                             params=(zonal, spherical, phase, ftype))
+            params = (zonal, spherical, phase, ftype)
+            (pre, act), wpk_b = _run_forward(lib, x, graph, plan, O, st, _param_packer(lib, params, st), addend=addend, bias=bias, params=params)
         ctx.save_for_backward(x, wpk_b, zonal, spherical, phase, bias, pre)
         ctx.graph, ctx.ftype, ctx.wshape, ctx.has_addend = graph, ftype, (O, I, R, F), addend is not None
         return act
@@ -440,7 +522,7 @@ class _FieldConvActFn(torch.autograd.Function):
             g_pre = torch.empty_like(pre)
             g_bias = torch.empty_like(bias)
             nbytes = lib.fc_tangent_nonlin_backward_workspace_bytes(N, O)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            ws = _scratch(nbytes, x.device)
             # the VJP's first kernel; its bias-gradient partials are summed by the convolution's finishing launch (one launch fewer)
             check(lib.fc_tangent_nonlin_backward_partial(_p(pre), _p(bias), _p(g_act), _p(g_pre), _p(ws), nbytes, N, O, st),
                   'fc_tangent_nonlin_backward_partial')
@@ -455,23 +537,15 @@ def field_conv_act(x, zonal, spherical, phase, ftype, band_limit, graph, bias, a
     complex64 or None.  Layers wider than the kernels' channel block fall back to the separate operators."""
     _require_device(x, 'field_conv')
     O, I = zonal.shape[0], zonal.shape[1]
-    if _run_time_path(x, graph):        # no specialised kernels for this (n_rings, band_limit), or double precision: separate operators
+    # separate operators: no specialised kernels for this (n_rings, band_limit) or double precision, more than one channel block, or
+    # the development switch
+    if _run_time_path(x, graph) or max(I, O) > _channel_block(graph, I, O, band_limit) or \
+            os.environ.get('FIELDCONV_NO_FUSED_EPILOGUE', '0') == '1':
         h = field_conv_params(x, zonal, spherical, phase, ftype, band_limit, graph)
         if addend is not None:
             h = h + addend
         return tangent_nonlin(h, bias)
-    blk = _channel_block(graph, I, O, band_limit)
-    if I > blk or O > blk or os.environ.get('FIELDCONV_NO_FUSED_EPILOGUE', '0') == '1':
-        h = field_conv_params(x, zonal, spherical, phase, ftype, band_limit, graph)
-        if addend is not None:
-            h = h + addend
-        return tangent_nonlin(h, bias)
-    if x.dtype != torch.complex64:
-        raise ValueError('field_conv expects complex64 features')
-    if x.dim() != 2 or x.shape[0] != graph.N or x.shape[1] != I:
-        raise ValueError(f'x has shape {tuple(x.shape)}, expected ({graph.N}, {I})')
-    if zonal.shape[2] != graph.R or 2 * band_limit + 1 != graph.F:
-        raise ValueError(f'stencil is (E,{graph.R},{graph.F}) but the filter has n_rings={zonal.shape[2]}, band_limit={band_limit}')
+    _check_conv(x, graph, I, zonal.shape[2], 2 * band_limit + 1)
     if bias.numel() != O:
         raise ValueError(f'bias has {bias.numel()} channels, the convolution {O}')
     if addend is not None and (addend.dtype != torch.complex64 or tuple(addend.shape) != (graph.n_targets, O)):
@@ -488,9 +562,9 @@ def _cgemm(lib, A, B, C, M, N, K, sam, sak, sbk, sbn, conj_b, alpha):
     """C (M,N) = alpha * A . op(B) on the matrix pipe (csrc/fc_cgemm.hip); strides in complex elements."""
     dt = _dtype_code(C)
     nbytes = lib.fc_cgemm_workspace_bytes(M, N, K, dt)          # > 0: a small output with a long contraction goes split along k
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=C.device) if nbytes else None
-    check(lib.fc_cgemm(_p(A), _p(B), _p(C), M, N, K, sam, sak, sbk, sbn, 1 if conj_b else 0, float(alpha), dt,
-                       _p(ws) if ws is not None else None, nbytes, _stream()), 'fc_cgemm')
+    ws = _scratch(nbytes, C.device, None)
+    check(lib.fc_cgemm(_p(A), _p(B), _p(C), M, N, K, sam, sak, sbk, sbn, 1 if conj_b else 0, float(alpha), dt, _po(ws), nbytes, _stream()),
+          'fc_cgemm')
     return C
 
 
@@ -521,8 +595,7 @@ class _GenericFieldConvFn(torch.autograd.Function):
     def _gather(lib, x, graph, I, R, B):
         F = 2 * B + 1
         contrib = torch.empty((graph.n_targets, I, R, F), dtype=x.dtype, device=x.device)
-        by_t = _csr(graph.rowptr_t, graph.nbr_t, None)
-        check(lib.fc_generic_gather(_p(x), _p(graph.sten_t), ctypes.byref(by_t), _p(contrib), graph.n_targets, I, R, B, _dtype_code(x),
+        check(lib.fc_generic_gather(_p(x), _p(graph.sten_t), ctypes.byref(_by_target(graph)), _p(contrib), graph.n_targets, I, R, B, _dtype_code(x),
                                     _stream()), 'fc_generic_gather')
         return contrib
 
@@ -542,8 +615,7 @@ class _GenericFieldConvFn(torch.autograd.Function):
             gw = torch.empty((O, I, R, F), dtype=x.dtype, device=x.device)
             _cgemm(lib, gy, contrib, gw, O, K, nt, 1, O, K, 1, True, 1.0 / F)             # gy^T . conj(contrib) / F
             gx = torch.empty_like(x)
-            by_s = _csr(graph.rowptr_s, graph.nbr_s, None)
-            check(lib.fc_generic_scatter(_p(x), _p(g_contrib), _p(graph.sten_s), ctypes.byref(by_s), _p(gx), graph.N, I, R, B, _dtype_code(x),
+            check(lib.fc_generic_scatter(_p(x), _p(g_contrib), _p(graph.sten_s), ctypes.byref(_by_source(graph)), _p(gx), graph.N, I, R, B, _dtype_code(x),
                                          _stream()), 'fc_generic_scatter')
         return gx, gw, None
 
@@ -554,13 +626,7 @@ def _generic_field_conv(x, w_eff, graph):
             raise _lib.FieldConvNativeError('complex128 features need a complex128 stencil (the support graph at hand was built from '
                                             'float32 data: records only)')
         raise _lib.FieldConvNativeError('the run-time FieldConv path needs a support graph with dense stencil rows')
-    if x.dtype not in (torch.complex64, torch.complex128) or w_eff.dtype != x.dtype or graph.sten_t.dtype != x.dtype:
-        raise ValueError(f'field_conv expects features, filter and stencil of one complex dtype, got {x.dtype}, {w_eff.dtype}, '
-                         f'{graph.sten_t.dtype}')
-    if x.dim() != 2 or x.shape[0] != graph.N or x.shape[1] != w_eff.shape[1]:
-        raise ValueError(f'x has shape {tuple(x.shape)}, expected ({graph.N}, {w_eff.shape[1]})')
-    if w_eff.shape[2] != graph.R or w_eff.shape[3] != graph.F:
-        raise ValueError(f'stencil is (E,{graph.R},{graph.F}) but the filter is {tuple(w_eff.shape)}')
+    _check_conv(x, graph, *w_eff.shape[1:], dtypes=(torch.complex64, torch.complex128), same=(w_eff, graph.sten_t))
     return _GenericFieldConvFn.apply(x, w_eff.contiguous(), graph)
 
 
@@ -596,13 +662,13 @@ class _WideFieldConvFn(torch.autograd.Function):
             O, I = zonal.shape[0], zonal.shape[1]
         dims = make_dims(graph, I, O, B)
         records = 1 if graph.factored else 0
-        kind, recs = (2, graph.geo_t) if graph.geo_t is not None else ((1, graph.rec_t) if graph.factored else (0, graph.sten_t))
+        kind, recs, _ = _records(graph)
         by_t = _csr(graph.rowptr_t, graph.nbr_t, graph.runs_t)
         with _on(x.device):
             nbytes = lib.fc_wide_workspace_bytes(ctypes.byref(dims), blk, records, 0)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            ws = _scratch(nbytes, x.device)
             y = torch.empty((graph.N, O), dtype=torch.complex64, device=x.device)
-            fp = None if explicit else FcFilterParams(zonal.data_ptr(), spherical.data_ptr(), phase.data_ptr(), ftype, None, None, None)
+            fp = None if explicit else _filter_params((zonal, spherical, phase, ftype))
             check(lib.fc_forward_wide(_p(x), _p(recs), ctypes.byref(by_t), kind, ctypes.byref(fp) if fp is not None else None,
                                       _p(w_eff) if explicit else None, _p(y), _p(ws), nbytes, ctypes.byref(dims), records, blk, _stream()),
                   'fc_forward_wide')
@@ -619,11 +685,11 @@ class _WideFieldConvFn(torch.autograd.Function):
         gy = gy.contiguous()
         dims = make_dims(graph, I, O, ctx.B)
         records = 1 if graph.factored else 0
-        sten = graph.rec_s if graph.factored else graph.sten_s
+        sten = _records(graph)[2]
         by_s = _csr(graph.rowptr_s, graph.nbr_s, graph.runs_s)
         with _on(x.device):
             nbytes = lib.fc_wide_workspace_bytes(ctypes.byref(dims), blk, records, 1)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            ws = _scratch(nbytes, x.device)
             gx = torch.empty_like(x)
             if ctx.explicit:
                 w_eff = ctx.saved_tensors[1]
@@ -631,24 +697,26 @@ class _WideFieldConvFn(torch.autograd.Function):
                 check(lib.fc_backward_wide(_p(x), _p(gy), _p(sten), ctypes.byref(by_s), records, None, _p(w_eff), _p(gw), _p(gx), _p(ws), nbytes,
                                            ctypes.byref(dims), blk, _stream()), 'fc_backward_wide')
                 return gx, None, None, None, gw, None, None, None, None
-            zonal, spherical, phase = ctx.saved_tensors[1:]
-            g_z, g_s = torch.empty_like(zonal), torch.empty_like(spherical)
-            g_p = torch.empty_like(phase) if ctx.ftype == 1 else None
-            fp = FcFilterParams(zonal.data_ptr(), spherical.data_ptr(), phase.data_ptr(), ctx.ftype, g_z.data_ptr(), g_s.data_ptr(),
-                                g_p.data_ptr() if g_p is not None else None)
+            params = (*ctx.saved_tensors[1:], ctx.ftype)
+            g_z, g_s, g_p = _param_grads(params)
+            fp = _filter_params(params, (g_z, g_s, g_p))
             check(lib.fc_backward_wide(_p(x), _p(gy), _p(sten), ctypes.byref(by_s), records, ctypes.byref(fp), None, None, _p(gx), _p(ws), nbytes,
                                        ctypes.byref(dims), blk, _stream()), 'fc_backward_wide')
         return gx, g_z, g_s, g_p, None, None, None, None, None
 
 
-def _wide_checks(x, graph, I, R, F):
-    if x.dtype != torch.complex64:
-        raise ValueError('field_conv expects complex64 features')
+def _check_conv(x, graph, I, R, F, dtypes=(torch.complex64,), same=(), wide=False):
+    """The argument checks of every convolution front end: features of one of `dtypes` (and the tensors of `same` -- an explicit filter,
+    a dense stencil -- of the features' dtype), x (N, I), a filter of the stencil's (n_rings, 2 band_limit + 1) = (R, F).  wide: a
+    layer of several channel blocks, which a partitioned mesh cannot run."""
+    if x.dtype not in dtypes or any(t.dtype != x.dtype for t in same):
+        raise ValueError(f"field_conv expects {', '.join(('features', 'filter', 'stencil')[:1 + len(same)])} of one dtype out of "
+                         f"{', '.join(str(d) for d in dtypes)}, got {', '.join(str(t.dtype) for t in (x, *same))}")
     if x.dim() != 2 or x.shape[0] != graph.N or x.shape[1] != I:
         raise ValueError(f'x has shape {tuple(x.shape)}, expected ({graph.N}, {I})')
     if R != graph.R or F != graph.F:
         raise ValueError(f'stencil is (E,{graph.R},{graph.F}) but the filter has n_rings={R}, 2 band_limit + 1 = {F}')
-    if graph.n_targets != graph.N or graph.forward_split is not None or graph.on_gx is not None:
+    if wide and (graph.n_targets != graph.N or graph.forward_split is not None or graph.on_gx is not None):
         raise _lib.FieldConvNativeError('layers wider than the channel block are not available on a partitioned mesh '
                                         '(restricted targets / exchange hooks)')
 
@@ -673,21 +741,14 @@ def field_conv_params(x, zonal, spherical, phase, ftype, band_limit, graph):
     (_WideFieldConvFn): the operator is linear in the input channels and independent across output channels."""
     _require_device(x, 'field_conv')
     O, I = zonal.shape[0], zonal.shape[1]
-    if _run_time_path(x, graph):
-        if zonal.shape[2] != graph.R or 2 * band_limit + 1 != graph.F:
-            raise ValueError(f'stencil is (E,{graph.R},{graph.F}) but the filter has n_rings={zonal.shape[2]}, band_limit={band_limit}')
+    if _run_time_path(x, graph):        # (_generic_field_conv checks the arguments)
         from .nn.field_conv import effective_filter          # the (tiny) assembly and its autograd in torch
         return _generic_field_conv(x, effective_filter(zonal, spherical, phase, int(ftype), int(band_limit)), graph)
     blk = _channel_block(graph, I, O, band_limit)
-    if I > blk or O > blk:              # channel blocks, enqueued natively (csrc/fc_wide.hip)
-        _wide_checks(x, graph, I, zonal.shape[2], 2 * band_limit + 1)
+    wide = I > blk or O > blk
+    _check_conv(x, graph, I, zonal.shape[2], 2 * band_limit + 1, wide=wide)
+    if wide:                            # channel blocks, enqueued natively (csrc/fc_wide.hip)
         return _WideFieldConvFn.apply(x, zonal, spherical, phase, None, int(ftype), int(band_limit), graph, int(blk))
-    if x.dtype != torch.complex64:
-        raise ValueError('field_conv expects complex64 features')
-    if x.dim() != 2 or x.shape[0] != graph.N or x.shape[1] != zonal.shape[1]:
-        raise ValueError(f'x has shape {tuple(x.shape)}, expected ({graph.N}, {zonal.shape[1]})')
-    if zonal.shape[2] != graph.R or 2 * band_limit + 1 != graph.F:
-        raise ValueError(f'stencil is (E,{graph.R},{graph.F}) but the filter has n_rings={zonal.shape[2]}, band_limit={band_limit}')
     return _FieldConvParamFn.apply(x, zonal, spherical, phase, int(ftype), int(band_limit), graph)
 
 
@@ -697,18 +758,13 @@ def field_conv(x, w_eff, graph):
     _require_device(x, 'field_conv')
     if x.dtype == torch.complex128:
         return _generic_field_conv(x, w_eff, graph)
-    if x.dtype != torch.complex64 or w_eff.dtype != torch.complex64:
-        raise ValueError('field_conv expects complex64 features and filters')
-    if x.dim() != 2 or x.shape[0] != graph.N or x.shape[1] != w_eff.shape[1]:
-        raise ValueError(f'x has shape {tuple(x.shape)}, expected ({graph.N}, {w_eff.shape[1]})')
-    if w_eff.shape[2] != graph.R or w_eff.shape[3] != graph.F:
-        raise ValueError(f'stencil is (E,{graph.R},{graph.F}) but the filter is {tuple(w_eff.shape)}')
-    O, I = w_eff.shape[0], w_eff.shape[1]
+    O, I, R, F = w_eff.shape
+    _check_conv(x, graph, I, R, F, same=(w_eff,))
     if not _compiled(graph):
         return _generic_field_conv(x, w_eff, graph)
     blk = _channel_block(graph, I, O, (graph.F - 1) // 2)
     if I > blk or O > blk:              # channel blocks, as in field_conv_params
-        _wide_checks(x, graph, I, w_eff.shape[2], w_eff.shape[3])
+        _check_conv(x, graph, I, R, F, wide=True)
         return _WideFieldConvFn.apply(x, None, None, None, w_eff, 0, (graph.F - 1) // 2, graph, int(blk))
     return _FieldConvFn.apply(x, w_eff, graph)
 
@@ -742,7 +798,7 @@ class _TangentLinFn(torch.autograd.Function):
             g_re = torch.empty_like(re_w)
             g_im = torch.empty_like(im_w)
             nbytes = lib.fc_tangent_lin_backward_workspace_bytes(N, I, O)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            ws = _scratch(nbytes, x.device)
             check(lib.fc_tangent_lin_backward(_p(x), _p(gy), _p(re_w), _p(im_w), _p(gx), _p(g_re), _p(g_im), _p(ws), nbytes,
                                               N, I, O, _stream()), 'fc_tangent_lin_backward')
         return gx, g_re, g_im
@@ -796,66 +852,57 @@ def tangent_lin(x, re_w, im_w):
     return _TangentLinFn.apply(x, re_w, im_w)
 
 
+def _nonlin_forward(ctx, x, bias, sfx):
+    """modReLU forward; sfx '' (float32, csrc/fc_pointwise.hip) or '_f64' (csrc/fc_pointwise_f64.hip) picks the entry points"""
+    lib = _lib.load()
+    x = x.contiguous()
+    b = bias.contiguous()
+    N, C = x.shape
+    name = 'fc_tangent_nonlin_forward' + sfx
+    with _on(x.device):
+        y = torch.empty_like(x)
+        check(getattr(lib, name)(_p(x), _p(b), _p(y), N, C, _stream()), name)
+    ctx.save_for_backward(x, b)
+    return y
+
+
+def _nonlin_backward(ctx, gy, sfx):
+    lib = _lib.load()
+    x, b = ctx.saved_tensors
+    N, C = x.shape
+    gy = gy.contiguous()
+    name = 'fc_tangent_nonlin_backward' + sfx
+    with _on(x.device):
+        gx = torch.empty_like(x)
+        gb = torch.empty_like(b)
+        nbytes = getattr(lib, 'fc_tangent_nonlin_backward_workspace_bytes' + sfx)(N, C)
+        ws = _scratch(nbytes, x.device)
+        check(getattr(lib, name)(_p(x), _p(b), _p(gy), _p(gx), _p(gb), _p(ws), nbytes, N, C, _stream()), name)
+    return gx, gb
+
+
 class _TangentNonLinFn(torch.autograd.Function):
     """reference nn/tangent_nonlin.py:24-35"""
 
     @staticmethod
     def forward(ctx, x, bias):
-        lib = _lib.load()
-        x = x.contiguous()
-        b = bias.contiguous()
-        N, C = x.shape
-        with _on(x.device):
-            y = torch.empty_like(x)
-            check(lib.fc_tangent_nonlin_forward(_p(x), _p(b), _p(y), N, C, _stream()), 'fc_tangent_nonlin_forward')
-        ctx.save_for_backward(x, b)
-        return y
+        return _nonlin_forward(ctx, x, bias, '')
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
-        x, b = ctx.saved_tensors
-        N, C = x.shape
-        gy = gy.contiguous()
-        with _on(x.device):
-            gx = torch.empty_like(x)
-            gb = torch.empty_like(b)
-            nbytes = lib.fc_tangent_nonlin_backward_workspace_bytes(N, C)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            check(lib.fc_tangent_nonlin_backward(_p(x), _p(b), _p(gy), _p(gx), _p(gb), _p(ws), nbytes, N, C, _stream()),
-                  'fc_tangent_nonlin_backward')
-        return gx, gb
+        return _nonlin_backward(ctx, gy, '')
 
 
 class _TangentNonLinF64Fn(torch.autograd.Function):
-    """reference nn/tangent_nonlin.py:24-35 in double precision (csrc/fc_pointwise_f64.hip)"""
+    """reference nn/tangent_nonlin.py:24-35 in double precision"""
 
     @staticmethod
     def forward(ctx, x, bias):
-        lib = _lib.load()
-        x = x.contiguous()
-        b = bias.contiguous()
-        N, C = x.shape
-        with _on(x.device):
-            y = torch.empty_like(x)
-            check(lib.fc_tangent_nonlin_forward_f64(_p(x), _p(b), _p(y), N, C, _stream()), 'fc_tangent_nonlin_forward_f64')
-        ctx.save_for_backward(x, b)
-        return y
+        return _nonlin_forward(ctx, x, bias, '_f64')
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
-        x, b = ctx.saved_tensors
-        N, C = x.shape
-        gy = gy.contiguous()
-        with _on(x.device):
-            gx = torch.empty_like(x)
-            gb = torch.empty_like(b)
-            nbytes = lib.fc_tangent_nonlin_backward_workspace_bytes_f64(N, C)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            check(lib.fc_tangent_nonlin_backward_f64(_p(x), _p(b), _p(gy), _p(gx), _p(gb), _p(ws), nbytes, N, C, _stream()),
-                  'fc_tangent_nonlin_backward_f64')
-        return gx, gb
+        return _nonlin_backward(ctx, gy, '_f64')
 
 
 def tangent_nonlin(x, bias):
@@ -923,6 +970,12 @@ def echo_slot_order(csr, ln, wxp, dtype=torch.complex64):
     return hit
 
 
+def _echo_outputs(x, dS):
+    """(complex histograms, their moduli: the descriptors), both (N, C, dS), in the precision of the features"""
+    hist = torch.empty((*x.shape, dS), dtype=x.dtype, device=x.device)
+    return hist, torch.empty(hist.shape, dtype=torch.float64 if x.dtype == torch.complex128 else torch.float32, device=x.device)
+
+
 class _EchoFn(torch.autograd.Function):
     """reference nn/echo.py:94-148 (ECHO.forward); any channel count: the entry points launch the channel blocks"""
 
@@ -933,10 +986,8 @@ class _EchoFn(torch.autograd.Function):
         N, C = x.shape
         dS = lib.fc_echo_hist_dim(n_bins)
         with _on(x.device):
-            hist = torch.empty((N, C, dS), dtype=torch.complex64, device=x.device)
-            desc = torch.empty((N, C, dS), dtype=torch.float32, device=x.device)
-            by_t = _csr(csr.rowptr_t, csr.nbr_t, None)
-            check(lib.fc_echo_forward(_p(x), _p(slots[0]), _p(slots[1]), ctypes.byref(by_t), _p(hist), _p(desc), N, csr.E, C, n_bins,
+            hist, desc = _echo_outputs(x, dS)
+            check(lib.fc_echo_forward(_p(x), _p(slots[0]), _p(slots[1]), ctypes.byref(_by_target(csr)), _p(hist), _p(desc), N, csr.E, C, n_bins,
                                       _stream()), 'fc_echo_forward')
         ctx.save_for_backward(x, hist)
         ctx.csr, ctx.n_bins, ctx.slots = csr, n_bins, slots
@@ -952,8 +1003,7 @@ class _EchoFn(torch.autograd.Function):
         with _on(x.device):
             gx = torch.empty_like(x)
             gh = torch.empty_like(hist)
-            by_s = _csr(csr.rowptr_s, csr.nbr_s, None)
-            check(lib.fc_echo_backward(_p(x), _p(slots[2]), _p(slots[3]), ctypes.byref(by_s), _p(hist), _p(g_desc), _p(gx), _p(gh), N, csr.E, C,
+            check(lib.fc_echo_backward(_p(x), _p(slots[2]), _p(slots[3]), ctypes.byref(_by_source(csr)), _p(hist), _p(g_desc), _p(gx), _p(gh), N, csr.E, C,
                                        ctx.n_bins, _stream()), 'fc_echo_backward')
         return gx, None, None, None
 
@@ -972,12 +1022,10 @@ class _EchoGenericFn(torch.autograd.Function):
             raise ValueError(f'ECHO: n_bins must be in 1..1024, got {n_bins}')
         dt = _dtype_code(x)
         with _on(x.device):
-            hist = torch.empty((N, C, dS), dtype=x.dtype, device=x.device)
-            desc = torch.empty((N, C, dS), dtype=x.real.dtype, device=x.device)
+            hist, desc = _echo_outputs(x, dS)
             nbytes = lib.fc_echo_generic_workspace_bytes(n_bins)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            by_t = _csr(csr.rowptr_t, csr.nbr_t, None)
-            check(lib.fc_echo_forward_generic(_p(x), _p(slots[0]), _p(slots[1]), ctypes.byref(by_t), _p(hist), _p(desc), _p(ws), nbytes, N,
+            ws = _scratch(nbytes, x.device)
+            check(lib.fc_echo_forward_generic(_p(x), _p(slots[0]), _p(slots[1]), ctypes.byref(_by_target(csr)), _p(hist), _p(desc), _p(ws), nbytes, N,
                                               csr.E, C, n_bins, dt, _stream()), 'fc_echo_forward_generic')
         ctx.save_for_backward(x, hist)
         ctx.csr, ctx.n_bins, ctx.slots = csr, n_bins, slots
@@ -994,9 +1042,8 @@ class _EchoGenericFn(torch.autograd.Function):
             gx = torch.empty_like(x)
             gh = torch.empty_like(hist)
             nbytes = lib.fc_echo_generic_workspace_bytes(ctx.n_bins)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            by_s = _csr(csr.rowptr_s, csr.nbr_s, None)
-            check(lib.fc_echo_backward_generic(_p(x), _p(slots[2]), _p(slots[3]), ctypes.byref(by_s), _p(hist), _p(g_desc), _p(gx), _p(gh),
+            ws = _scratch(nbytes, x.device)
+            check(lib.fc_echo_backward_generic(_p(x), _p(slots[2]), _p(slots[3]), ctypes.byref(_by_source(csr)), _p(hist), _p(g_desc), _p(gx), _p(gh),
                                                _p(ws), nbytes, N, csr.E, C, ctx.n_bins, _dtype_code(x), _stream()), 'fc_echo_backward_generic')
         return gx, None, None, None
 
@@ -1016,6 +1063,21 @@ def echo_descriptors(x, supp_edges, ln, wxp, n_bins):
     if x.dtype == torch.complex128 or _lib.load().fc_echo_hist_dim(n_bins) == 0:
         return _EchoGenericFn.apply(x, slots, csr, n_bins)
     return _EchoFn.apply(x, slots, csr, n_bins)
+
+
+def _trans_field_outputs(x, O, R):
+    """(y (N,O), angular sums (N,Cin,R), magnitude sums (N,Cin,R), ring sums (N,R)) of TransField for real features x (N,Cin): complex
+    except the magnitudes, in the precision of x"""
+    N, Cin = x.shape
+    cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+    return (torch.empty((N, O), dtype=cdt, device=x.device), torch.empty((N, Cin, R), dtype=cdt, device=x.device),
+            torch.empty((N, Cin, R), dtype=x.dtype, device=x.device), torch.empty((N, R), dtype=cdt, device=x.device))
+
+
+def _trans_field_grads(mag, Cin, zonal_ang, zonal_mag, phase, ftype):
+    """(gx (N,Cin) real, g_zonal_ang, g_zonal_mag, g_phase or None: the phase offsets are parameters unless ftype is 0), uninitialised"""
+    return (torch.empty((mag.shape[0], Cin), dtype=mag.dtype, device=mag.device), torch.empty_like(zonal_ang), torch.empty_like(zonal_mag),
+            torch.empty_like(phase) if ftype != 0 else None)
 
 
 class _TransFieldFn(torch.autograd.Function):
@@ -1045,12 +1107,8 @@ class _TransFieldFn(torch.autograd.Function):
         O, _, R = zonal_ang.shape
         zonal_ang, zonal_mag, phase = zonal_ang.contiguous(), zonal_mag.contiguous(), phase.contiguous()
         with _on(x.device):
-            y = torch.empty((N, O), dtype=torch.complex64, device=x.device)
-            ang = torch.empty((N, Cin, R), dtype=torch.complex64, device=x.device)
-            mag = torch.empty((N, Cin, R), dtype=torch.float32, device=x.device)
-            s1sum = torch.empty((N, R), dtype=torch.complex64, device=x.device)
-            by_t = _csr(csr.rowptr_t, csr.nbr_t, None)
-            check(lib.fc_trans_field_forward(_p(x), _p(sten), ctypes.byref(by_t), _p(csr.perm_t), _p(zonal_ang), _p(zonal_mag),
+            y, ang, mag, s1sum = _trans_field_outputs(x, O, R)
+            check(lib.fc_trans_field_forward(_p(x), _p(sten), ctypes.byref(_by_target(csr)), _p(csr.perm_t), _p(zonal_ang), _p(zonal_mag),
                                              _p(phase), _p(y), _p(ang), _p(mag), _p(s1sum), N, csr.E, Cin, O, R, stride, _stream()),
                   'fc_trans_field_forward')
         ctx.save_for_backward(sten, zonal_ang, zonal_mag, phase, ang, mag, s1sum)
@@ -1066,15 +1124,12 @@ class _TransFieldFn(torch.autograd.Function):
         N = ang.shape[0]
         gy = gy.contiguous()
         with _on(gy.device):
-            gx = torch.empty((N, Cin), dtype=torch.float32, device=gy.device)
-            g_za, g_zm = torch.empty_like(zonal_ang), torch.empty_like(zonal_mag)
-            g_ph = torch.empty_like(phase) if ctx.ftype != 0 else None
+            gx, g_za, g_zm, g_ph = _trans_field_grads(mag, Cin, zonal_ang, zonal_mag, phase, ctx.ftype)
             nbytes = lib.fc_trans_field_backward_workspace_bytes(N, Cin, O, R)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
-            by_s = _csr(csr.rowptr_s, csr.nbr_s, None)
-            check(lib.fc_trans_field_backward(_p(sten), ctypes.byref(by_s), _p(csr.perm_s), _p(zonal_ang), _p(zonal_mag), _p(phase),
+            ws = _scratch(nbytes, gy.device)
+            check(lib.fc_trans_field_backward(_p(sten), ctypes.byref(_by_source(csr)), _p(csr.perm_s), _p(zonal_ang), _p(zonal_mag), _p(phase),
                                               _p(ang), _p(mag), _p(s1sum), _p(gy), _p(gx), _p(g_za), _p(g_zm),
-                                              _p(g_ph) if g_ph is not None else None, _p(ws), nbytes, N, csr.E, Cin, O, R,
+                                              _po(g_ph), _p(ws), nbytes, N, csr.E, Cin, O, R,
                                               ctx.stride, ctx.ftype, _stream()), 'fc_trans_field_backward')
         return gx, None, None, g_za, g_zm, g_ph, None, None
 
@@ -1093,15 +1148,10 @@ class _TransFieldGenericFn(torch.autograd.Function):
         O, _, R = zonal_ang.shape
         stride = int(sten.shape[2])
         zonal_ang, zonal_mag, phase = zonal_ang.contiguous(), zonal_mag.contiguous(), phase.contiguous()
-        cdt = torch.complex128 if x.dtype == torch.float64 else torch.complex64
         dt = _dtype_code(x)
         with _on(x.device):
-            y = torch.empty((N, O), dtype=cdt, device=x.device)
-            ang = torch.empty((N, Cin, R), dtype=cdt, device=x.device)
-            mag = torch.empty((N, Cin, R), dtype=x.dtype, device=x.device)
-            s1sum = torch.empty((N, R), dtype=cdt, device=x.device)
-            by_t = _csr(csr.rowptr_t, csr.nbr_t, None)
-            check(lib.fc_trans_field_forward_generic(_p(x), _p(sten), ctypes.byref(by_t), _p(csr.perm_t), _p(zonal_ang), _p(zonal_mag),
+            y, ang, mag, s1sum = _trans_field_outputs(x, O, R)
+            check(lib.fc_trans_field_forward_generic(_p(x), _p(sten), ctypes.byref(_by_target(csr)), _p(csr.perm_t), _p(zonal_ang), _p(zonal_mag),
                                                      _p(phase), _p(y), _p(ang), _p(mag), _p(s1sum), N, csr.E, Cin, O, R, stride, dt, _stream()),
                   'fc_trans_field_forward_generic')
         ctx.save_for_backward(sten, zonal_ang, zonal_mag, phase, ang, mag, s1sum)
@@ -1117,15 +1167,12 @@ class _TransFieldGenericFn(torch.autograd.Function):
         N = ang.shape[0]
         gy = gy.contiguous()
         with _on(gy.device):
-            gx = torch.empty((N, Cin), dtype=mag.dtype, device=gy.device)
-            g_za, g_zm = torch.empty_like(zonal_ang), torch.empty_like(zonal_mag)
-            g_ph = torch.empty_like(phase) if ctx.ftype != 0 else None
+            gx, g_za, g_zm, g_ph = _trans_field_grads(mag, Cin, zonal_ang, zonal_mag, phase, ctx.ftype)
             nbytes = lib.fc_trans_field_backward_generic_workspace_bytes(N, Cin, O, R, ctx.dt)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
-            by_s = _csr(csr.rowptr_s, csr.nbr_s, None)
-            check(lib.fc_trans_field_backward_generic(_p(sten), ctypes.byref(by_s), _p(csr.perm_s), _p(zonal_ang), _p(zonal_mag), _p(phase),
+            ws = _scratch(nbytes, gy.device)
+            check(lib.fc_trans_field_backward_generic(_p(sten), ctypes.byref(_by_source(csr)), _p(csr.perm_s), _p(zonal_ang), _p(zonal_mag), _p(phase),
                                                       _p(ang), _p(mag), _p(s1sum), _p(gy), _p(gx), _p(g_za), _p(g_zm),
-                                                      _p(g_ph) if g_ph is not None else None, _p(ws), nbytes, N, csr.E, Cin, O, R, ctx.stride,
+                                                      _po(g_ph), _p(ws), nbytes, N, csr.E, Cin, O, R, ctx.stride,
                                                       ctx.ftype, ctx.dt, _stream()), 'fc_trans_field_backward_generic')
         return gx, None, g_za, g_zm, g_ph, None, None
 

@@ -506,31 +506,33 @@ class _CountingLibrary:
     """The real library with every ENQUEUEING entry point (the ones that take a stream) replaced by a recorder that returns
     FC_OK: the host side of a network step -- module dispatch, autograd nodes, buffer carving, struct filling -- runs
     unchanged on CPU tensors, nothing is launched, and every crossing into the library is counted.  Pure host queries
-    (sizes, fc_supported, ...) pass through to the real functions and are counted as well."""
+    (sizes, fc_supported, ...) pass through to the real functions and are counted as well.  `trace` keeps, per call, the symbol
+    and its arguments: numbers as they are, every pointer (c_void_p, byref, None) as 'ptr' or 'null'."""
 
     def __init__(self, real, header):
-        self.real, self.calls = real, []
+        self.real, self.calls, self.trace = real, [], []
         self.enqueue = set(re.findall(r'\b(fc_[a-z0-9_]+)\s*\([^;]*?void\*\s*stream\)', header, flags=re.S))
+
+    @staticmethod
+    def _arg(a):
+        if isinstance(a, (int, float)):
+            return a
+        if isinstance(a, ctypes.c_void_p):
+            return 'ptr' if a.value else 'null'
+        return 'null' if a is None else 'ptr'
 
     def __getattr__(self, name):
         fn = getattr(self.real, name)
-        if name in self.enqueue:
-            def rec(*args):
-                self.calls.append(name)
-                return 0
-            return rec
 
-        def passthrough(*args):
+        def call(*args):
             self.calls.append(name)
-            return fn(*args)
-        return passthrough
+            self.trace.append([name, [self._arg(a) for a in args]])
+            return 0 if name in self.enqueue else fn(*args)
+        return call
 
 
-def test_config3_step_takes_at_most_40_foreign_calls(monkeypatch):
-    """BASELINE configs[2]'s network (LiftBlock, four FCResNetBlocks, ECHOBlock: nine convolutions; reference
-    segmentation.ipynb:196-236) forward + loss + backward: how often does the binding cross into the library?  One call per block and
-    pass = 12 (+ 2 for ECHOBlock's dense tail, fc_echo_head_*), where the per-operator path took ~80 (16 per FCResNetBlock).  The reference trains with batch size 1 on a different
-    ~1k-vertex mesh every step (segmentation.ipynb:120,137), so the host's per-step cost is what a training run sees."""
+def _config3_network(monkeypatch):
+    """BASELINE configs[2]'s network on a 300-vertex sphere, bound to a _CountingLibrary -> (library, one training step)"""
     from fieldconv_amd import blocks, functional
     header = open(os.path.join(ROOT, 'include', 'fieldconv_hip.h')).read()
     counting = _CountingLibrary(_lib.load(), header)
@@ -566,6 +568,16 @@ def test_config3_step_takes_at_most_40_foreign_calls(monkeypatch):
         loss = torch.nn.functional.nll_loss(torch.nn.functional.log_softmax(logits, dim=1), labels)
         return torch.autograd.grad(loss, params, allow_unused=True)
 
+    return counting, step
+
+
+def test_config3_step_takes_at_most_40_foreign_calls(monkeypatch):
+    """BASELINE configs[2]'s network (LiftBlock, four FCResNetBlocks, ECHOBlock: nine convolutions; reference
+    segmentation.ipynb:196-236) forward + loss + backward: how often does the binding cross into the library?  One call per block and
+    pass = 12 (+ 2 for ECHOBlock's dense tail, fc_echo_head_*), where the per-operator path took ~80 (16 per FCResNetBlock).  The reference trains with batch size 1 on a different
+    ~1k-vertex mesh every step (segmentation.ipynb:120,137), so the host's per-step cost is what a training run sees."""
+    from fieldconv_amd import functional
+    counting, step = _config3_network(monkeypatch)
     step()                                   # first step on a mesh: plans, sizes and slot orders are computed and cached
     first = list(counting.calls)
     counting.calls.clear()
@@ -584,3 +596,34 @@ def test_config3_step_takes_at_most_40_foreign_calls(monkeypatch):
     counting.calls.clear()
     step()
     assert len(counting.calls) > 2 * len(steady), (len(counting.calls), len(steady))
+
+
+def test_config3_step_makes_the_recorded_foreign_calls(monkeypatch):
+    """The steady-state step of the test above, call by call: symbol, order, every integer / size argument and which pointers are
+    NULL, on the block-level path, the per-operator path and the one-call-per-kernel path.  tests/golden/host_call_trace.json was
+    recorded with this recorder before the binding's launch idioms were merged into single helpers (on commit 8f5b314) and is
+    not regenerated from later code: a change of the binding that alters a foreign call shows here."""
+    import json
+    from fieldconv_amd import functional
+    counting, step = _config3_network(monkeypatch)
+    monkeypatch.setattr(functional, '_require_device', lambda t, what: None)
+    modes = {'block': {}, 'operator': {'FIELDCONV_BLOCK_CALLS': '0'},
+             'separate': {'FIELDCONV_BLOCK_CALLS': '0', 'FIELDCONV_SEPARATE_CALLS': '1'}}
+    traces = {}
+    for mode, env in modes.items():
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        if 'FIELDCONV_SEPARATE_CALLS' in env:
+            monkeypatch.setattr(functional, '_ONE_CALL', False)      # (read at import)
+        step()                                   # plans, sizes and slot orders of this path
+        counting.trace.clear()
+        step()
+        traces[mode] = json.loads(json.dumps(counting.trace))
+    path = os.path.join(ROOT, 'tests', 'golden', 'host_call_trace.json')
+    golden = json.load(open(path))
+    assert set(golden) == set(modes)
+    for mode in modes:
+        assert len(traces[mode]) == len(golden[mode]), (mode, len(traces[mode]), len(golden[mode]))
+        for i, (got, want) in enumerate(zip(traces[mode], golden[mode])):
+            assert got == want, (mode, i, got, want)
+    assert len(traces['block']) < len(traces['operator']) < len(traces['separate'])
