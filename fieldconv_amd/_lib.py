@@ -196,6 +196,9 @@ SIGNATURES = {
     'fc_segment_pool_soft_abs_backward': (ctypes.c_int, [_vp, _vp, _vp] + [_c_int32] * 5 + [_vp, _vp]),
     'fc_segment_pool_forward': (ctypes.c_int, [_vp, _vp] + [_c_int32] * 5 + [_vp, _vp, _sz, _vp]),
     'fc_segment_pool_backward': (ctypes.c_int, [_vp, _vp] + [_c_int32] * 5 + [_vp, _vp]),
+    'fc_match_workspace_bytes': (_sz, [_c_int32] * 3),
+    'fc_match_topk': (ctypes.c_int, [_vp, _c_int32, _vp, _c_int32, _c_int32, _c_int32, _vp, _vp, _c_int32, _vp, _c_int32, _c_int32, _vp, _vp,
+                                     _vp, _sz, _vp]),
 }
 
 _LIB = None

@@ -9,39 +9,15 @@
 // Sums over pairs / rows that end in one scalar run in double in a fixed order (wavefront, then workgroup, then one workgroup over
 // the per-workgroup partials in index order): two runs give the same bits.
 #include "../../include/fieldconv_hip.h"
-#include "fc_common.hpp"
+#include "fc_pair.hpp"          // d2_step / pair_d2 and the dense tile: shared with fc_match.hip
 
 namespace fc {
 
 constexpr int kLossThreads = 1024;          // workgroup of the kernels that end in a scalar: one pair / row (group) per thread
 constexpr int kLossWaves = kLossThreads / 64;
 constexpr int kGradThreads = 256;
-constexpr int kDenseThreads = 256;          // 16 x 16 lanes, each owning 4 x 4 pairs of a 64 x 64 tile
-constexpr int kDenseTile = 64;
-constexpr int kDenseChunk = 16;             // channels staged per pass
-constexpr int kDensePitch = kDenseTile + 4; // row pitch of the transposed LDS tiles (keeps 16-byte alignment, spreads the banks)
 constexpr int kDenseMaxThr = 16;
 constexpr int kDenseMaxGrid = 2048;
-
-// acc + t*t with t = a - b; a distance starts from acc = 0 (0 + t*t == t*t exactly).
-template <typename T>
-__device__ __forceinline__ T d2_step(T acc, T a, T b) {
-#pragma clang fp contract(off)          // (plain operators: __fmul_rn / __fadd_rn are header functions that hipcc contracts)
-    const T t = a - b;
-    return acc + t * t;
-}
-
-template <typename T>
-__device__ __forceinline__ T pair_d2(const T* __restrict__ a, const T* __restrict__ b, int C) {
-    T acc = 0;
-    for (int c = 0; c < C; ++c) acc = d2_step(acc, a[c], b[c]);
-    return acc;
-}
-
-template <typename T>
-__device__ __forceinline__ T quiet_nan() {
-    return static_cast<T>(__int_as_float(0x7fc00000));
-}
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -353,12 +329,7 @@ namespace {
 
 size_t round256(size_t b) { return (b + 255) / 256 * 256; }
 
-constexpr int64_t kMaxRows = (int64_t)1 << 24;          // rows_fit_32bit's row limit (fc_api.hip)
-
-bool features_ok(const void* xS, int32_t nS, const void* xT, int32_t nT, int32_t C, int32_t dtype) {
-    return xS && xT && nS >= 1 && nT >= 1 && nS < kMaxRows && nT < kMaxRows && C >= 1 && (dtype == 0 || dtype == 1) &&
-           (uint64_t)(nS > nT ? nS : nT) * (uint64_t)C * 8u < ((uint64_t)1 << 32);
-}
+using fc::features_ok;
 
 int launch_status() { return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH; }
 

@@ -91,3 +91,26 @@ def twin_eval_curve(xS, xT, pos_pairs, thresholds):
     n_fn = (d_listed[None, :] > thr[:, None]).sum(1)
     n_fp = below - (d_distinct[None, :] < thr[:, None]).sum(1)
     return n_fn, n_fp
+
+
+def hard_null_pairs(xS, xT, pos_pairs, per_row=1):
+    """(R * per_row, 2) int64 hard negatives: for each distinct xT row a of pos_pairs, in ascending order, the per_row (1..8)
+    rows of xS nearest to xT[a] that are not a's positive, nearest first -- the non-matching pairs a descriptor confuses most,
+    where a uniform draw (sample_null_pairs) is almost always already far apart.  One match_descriptors call with the positives
+    excluded (fieldconv_amd.matching; the losses' d2, ties to the lower row).  A row with more than one distinct positive raises
+    ValueError.  Slots without a candidate (xS has fewer than per_row + 1 rows, NaN features) are dropped, so fewer rows can
+    come back; the result is a valid n_ for twin_loss.  The positives are checked and the row count is read back on the host."""
+    from ..matching import match_descriptors
+    if not torch.is_tensor(xS) or not torch.is_tensor(xT) or xS.dim() != 2 or xT.dim() != 2:
+        raise ValueError('hard_null_pairs: xS and xT must be (N,C) tensors')
+    n_T, n_S = int(xT.shape[0]), int(xS.shape[0])
+    lin = _sorted_positive_index(pos_pairs, n_T, n_S, 'hard_null_pairs')
+    rows, true_row = torch.div(lin, n_S, rounding_mode='floor'), lin % n_S
+    if rows.numel() > 1 and bool((rows[1:] == rows[:-1]).any()):
+        raise ValueError('hard_null_pairs: a row of xT has more than one distinct positive (one row of xS can be excluded per row)')
+    exclude = torch.full((n_T,), -1, dtype=torch.int64, device=pos_pairs.device)
+    exclude[rows] = true_row
+    idx, _ = match_descriptors(xS, xT, k=per_row, exclude=exclude)
+    near = idx[rows]                                                    # (R, per_row), nearest first
+    pairs = torch.stack((rows[:, None].expand_as(near), near), 2).reshape(-1, 2)
+    return pairs[pairs[:, 1] >= 0]

@@ -658,6 +658,32 @@ int fc_segment_pool_forward(const void* x, const int64_t* ptr, int32_t N, int32_
 int fc_segment_pool_backward(const void* grad_out, const int64_t* ptr, int32_t N, int32_t B, int32_t C, int32_t dtype, int32_t reduce,
                              void* grad_x, void* stream);
 
+/* ---- descriptor matching: the k nearest rows of xS for every row of xT (csrc/fc_match.hip) ---------------------------- *
+ * Features and distance as in the losses section above: xS (N_S,C), xT (N_T,C), dtype 0 = float32, 1 = float64, d2(a,b) the
+ * SAME bits as fc_pair_sqdist and fc_twin_count_dense (one definition, csrc/fc_pair.hpp); the same limits on N and C.
+ * match topk         for every row a of xT the k rows b of xS with the smallest d2(a,b), ordered by the pair (d2, b) ascending:
+ *                    an exact tie goes to the lower row.  idx (N_T,k) int64 row numbers of xS, d2 (N_T,k) of the dtype;
+ *                    1 <= k <= 8.  A NaN distance is never a match.  A slot without a candidate (fewer than k rows to search,
+ *                    an excluded row, NaN distances) holds idx = -1, d2 = +inf.
+ *                    ptr_S, ptr_T: both null, or (B+1) int64 tables in DEVICE memory of ascending ranges (ptr[0] = 0, ptr[B] = N),
+ *                    checked by the CALLER: the rows ptr_T[m] .. ptr_T[m+1] - 1 of xT search the rows ptr_S[m] .. ptr_S[m+1] - 1
+ *                    of xS only (the meshes of two mini-batches); idx stays a row number of the whole xS.  The kernels clamp
+ *                    what they read from the tables: a malformed table gives a meaningless result but no access outside the
+ *                    buffers.  B >= 1, N_T + 64 B < 2^31.
+ *                    exclude: null, or (N_T) int64 in device memory: the one row of xS that row a skips; a value outside
+ *                    [0, N_S) (-1 by convention) skips nothing.
+ *                    parts: the xS range of every 64-row tile of xT is searched by `parts` workgroups (1 <= parts <= 1024), each
+ *                    leaving its k best in the workspace, and a second launch merges them; parts = 1 is one launch and needs
+ *                    no workspace; parts = 0 lets the library choose (enough workgroups to fill the card when N_T is small,
+ *                    no part shorter than 4 tiles of xS).  The order (d2, b) is total, so the result does not depend on parts.
+ * No atomics: two runs give the same bits.  Workspace: the query below, O(N_T k parts) bytes whatever N_S is (0 for parts = 1;
+ * for parts = 0 sized for the most parts the library may choose for N_T rows); FC_ERR_WORKSPACE when it is missing or smaller.
+ * No allocation or synchronisation inside. */
+size_t fc_match_workspace_bytes(int32_t N_T, int32_t k, int32_t parts);
+int fc_match_topk(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int32_t C, int32_t dtype, const int64_t* ptr_S,
+                  const int64_t* ptr_T, int32_t B, const int64_t* exclude, int32_t k, int32_t parts, int64_t* idx, void* d2,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
