@@ -199,6 +199,13 @@ SIGNATURES = {
     'fc_match_workspace_bytes': (_sz, [_c_int32] * 3),
     'fc_match_topk': (ctypes.c_int, [_vp, _c_int32, _vp, _c_int32, _c_int32, _c_int32, _vp, _vp, _c_int32, _vp, _c_int32, _c_int32, _vp, _vp,
                                      _vp, _sz, _vp]),
+    'fc_linear_ce_workspace_bytes': (_sz, [_c_int32] * 6),
+    'fc_linear_ce_forward': (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_int32, _c_int32, _c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
+                                            _c_int32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'fc_linear_topk': (ctypes.c_int, [_vp, _vp, _vp] + [_c_int32] * 5 + [_vp, _vp, _vp, _sz, _vp]),
+    'fc_linear_ce_backward_input': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 3 + [ctypes.c_double, ctypes.c_double, ctypes.c_int64, _vp, _vp]),
+    'fc_linear_ce_backward_weight': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 3 + [ctypes.c_double, ctypes.c_double, ctypes.c_int64, _c_int32,
+                                                    _vp, _vp, _vp, _sz, _vp]),
 }
 
 _LIB = None

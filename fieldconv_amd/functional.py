@@ -953,6 +953,7 @@ def soft_abs(x):
 
 from .pooling import mesh_mean, mesh_pool          # noqa: E402,F401  (per-mesh pooling over a MeshBatch: csrc/fc_segment.hip)
 from .matching import match_accuracy, match_descriptors, mutual_matches          # noqa: E402,F401  (nearest rows: csrc/fc_match.hip)
+from .head import linear_cross_entropy, linear_logsumexp, linear_topk, vertex_accuracy          # noqa: E402,F401  (the fused classification head: csrc/fc_linear_ce.hip)
 
 
 def _tkey(t):

@@ -11,6 +11,9 @@ from .label_smoothing_loss import LabelSmoothingLoss
 from .twin_loss import TwinLoss
 from .twin_eval import TwinEval
 from .mesh_pool import MeshPool
+from .linear_cross_entropy import LinearCrossEntropy
+from ..head import vertex_accuracy
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
-           'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval', 'MeshPool']
+           'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval',
+           'LinearCrossEntropy', 'vertex_accuracy', 'MeshPool']

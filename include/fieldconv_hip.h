@@ -684,6 +684,43 @@ int fc_match_topk(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int3
                   const int64_t* ptr_T, int32_t B, const int64_t* exclude, int32_t k, int32_t parts, int64_t* idx, void* d2,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- vertex-classification head: linear layer fused with cross-entropy / top-k prediction (csrc/fc_linear_ce.hip) ------ *
+ * z = h W^T + b with h (N,H), weight (K,H), bias (K) or null (a torch.nn.Linear), float32 only.  The N x K logits are never
+ * stored: every kernel recomputes the 64 x 64 tile it needs with one routine on the fp32 matrix pipe, so a logit has the same
+ * bits in the loss, in the gradients and in the prediction.  target (N) int64 in DEVICE memory.
+ * forward            lse[n] = log sum_k exp z[n,k]; loss_rows[n] = lse[n] - sum_k q[n,k] z[n,k] with q = confidence at the
+ *                    target and off_value elsewhere (the caller keeps confidence + (K-1) off_value = 1); 0 where target[n] ==
+ *                    ignore_index; NaN for any other target outside [0,K) (nothing is read for it).  total[0] = the sum of
+ *                    loss_rows, total[1] = total[0] / total[2], total[2] = the number of rows whose target is not ignore_index
+ *                    (three floats; the sums run in double in a fixed order).
+ * topk               idx (N,k) int64, z (N,k): the k <= 8 classes with the largest logits per row ordered by (z descending,
+ *                    class ascending): an exact tie goes to the lower class; a NaN logit sorts after every number; slots beyond
+ *                    K hold idx = -1, z = -inf.
+ * backward input     grad_h (N,H) = G weight,  G[n,k] = row_scale[n] (exp(z[n,k] - lse[n]) - q[n,k]); a row whose target is
+ *                    ignore_index has G = 0 whatever row_scale holds, a row whose target is otherwise outside [0,K) has G = NaN.
+ * backward weight    grad_weight (K,H) = G^T h and grad_bias (K) = the column sums of G; either may be null (not both).
+ * parts              forward / topk: the classes of every 64-row tile are walked by `parts` workgroups whose per-row results a
+ *                    second launch merges in part order; backward weight: the rows of every 64-class tile likewise, the
+ *                    partial sums added in part order.  0 <= parts <= 64; 0 lets the library choose (enough workgroups to
+ *                    fill the card, no part shorter than 4 tiles).  parts changes the order of the sums (the last bits), never
+ *                    the top-k result (a total order).
+ * No atomics: two runs give the same bits.  Workspace: the query below with pass 0 = forward, 1 = backward weight, 2 = topk
+ * (k matters for pass 2 only): O(N parts), O(K H parts) (0 for parts = 1) and O(N k parts) bytes; for parts = 0 sized for the
+ * most parts the library may choose; FC_ERR_WORKSPACE when it is missing or smaller.  No allocation or synchronisation inside. */
+size_t fc_linear_ce_workspace_bytes(int32_t N, int32_t H, int32_t K, int32_t parts, int32_t pass, int32_t k);
+int fc_linear_ce_forward(const float* h, const float* weight, const float* bias, const int64_t* target, int32_t N, int32_t H, int32_t K,
+                         double confidence, double off_value, int64_t ignore_index, int32_t parts, float* lse, float* loss_rows,
+                         float* total, void* workspace, size_t workspace_bytes, void* stream);
+int fc_linear_topk(const float* h, const float* weight, const float* bias, int32_t N, int32_t H, int32_t K, int32_t k, int32_t parts,
+                   int64_t* idx, float* z, void* workspace, size_t workspace_bytes, void* stream);
+int fc_linear_ce_backward_input(const float* h, const float* weight, const float* bias, const int64_t* target, const float* lse,
+                                const float* row_scale, int32_t N, int32_t H, int32_t K, double confidence, double off_value,
+                                int64_t ignore_index, float* grad_h, void* stream);
+int fc_linear_ce_backward_weight(const float* h, const float* weight, const float* bias, const int64_t* target, const float* lse,
+                                 const float* row_scale, int32_t N, int32_t H, int32_t K, double confidence, double off_value,
+                                 int64_t ignore_index, int32_t parts, float* grad_weight, float* grad_bias, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
