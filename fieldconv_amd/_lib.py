@@ -206,6 +206,14 @@ SIGNATURES = {
     'fc_linear_ce_backward_input': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 3 + [ctypes.c_double, ctypes.c_double, ctypes.c_int64, _vp, _vp]),
     'fc_linear_ce_backward_weight': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 3 + [ctypes.c_double, ctypes.c_double, ctypes.c_int64, _c_int32,
                                                     _vp, _vp, _vp, _sz, _vp]),
+    'fc_geodesic_lds_vertices': (_c_int32, []),
+    'fc_mesh_edge_lengths': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _vp]),
+    'fc_geodesic_rows': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _c_int32, _vp, _vp, _vp]),
+    'fc_geodesic_workspace_bytes': (_sz, [_c_int32, _c_int32]),
+    'fc_geodesic_nearest': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _vp, _vp, _c_int32, _c_int32, _c_int32, _vp, _vp, _vp, _vp,
+                                           _sz, _vp]),
+    'fc_face_areas': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp]),
+    'fc_segment_sum_f32': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _c_int32, ctypes.c_float, _vp, _vp]),
 }
 
 _LIB = None

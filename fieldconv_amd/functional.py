@@ -1207,3 +1207,5 @@ def trans_field(x, supp_edges, lift_sten, zonal_ang, zonal_mag, phase, ftype):
         return _TransFieldGenericFn.apply(x, lift_sten, zonal_ang, zonal_mag, phase, csr, int(ftype))
     sten, stride = _TransFieldFn._stencil(lift_sten)
     return _TransFieldFn.apply(x, sten, stride, zonal_ang, zonal_mag, phase, csr, int(ftype))
+from .geodesic import (compose_map, correspondence_curve, geodesic_distances, geodesic_error, mesh_edge_graph, nearest_sample,          # noqa: E402,F401  (mesh geodesics: csrc/fc_geodesic.hip)
+                       sample_weights, samples_to_nearest, vertex_masses)

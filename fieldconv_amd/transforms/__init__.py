@@ -1,8 +1,11 @@
 from .fc_precomp import FCPrecomp
 from .normalize import NormalizeArea, NormalizeAxes
 from .precomp_cache import load_precomp, save_precomp
+from .sample_weights import SampleWeights
 from .support_graph import (SupportGraph, farthest_point_sample, farthest_point_sample_batched, radius_edges,
                             radius_edges_batched)
+from ..geodesic import geodesic_distances, mesh_edge_graph, nearest_sample, sample_weights
 
 __all__ = ['FCPrecomp', 'NormalizeArea', 'NormalizeAxes', 'SupportGraph', 'farthest_point_sample', 'load_precomp', 'radius_edges',
-           'save_precomp', 'farthest_point_sample_batched', 'radius_edges_batched']
+           'save_precomp', 'farthest_point_sample_batched', 'radius_edges_batched', 'SampleWeights', 'geodesic_distances',
+           'mesh_edge_graph', 'nearest_sample', 'sample_weights']

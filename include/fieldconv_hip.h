@@ -721,6 +721,50 @@ int fc_linear_ce_backward_weight(const float* h, const float* weight, const floa
                                  int64_t ignore_index, int32_t parts, float* grad_weight, float* grad_bias, void* workspace,
                                  size_t workspace_bytes, void* stream);
 
+/* ---- mesh geodesics over the edge graph: distance rows, nearest source (csrc/fc_geodesic.hip) ---------------------------- *
+ * The graph is a CSR over the vertices (rowptr (V+1), nbr (E) int32: the undirected triangle sides in both directions,
+ * neighbours ascending; built by the caller) with one float32 length per slot.  This is the edge-graph metric, not the heat
+ * method of the reference's fcutils: it overestimates the true geodesic by up to a few percent.
+ * edge lengths       length[e] = sqrt((dx dx + dy dy) + dz dz) between pos[src[e]] and pos[nbr[e]] (src: the row of slot e), every
+ *                    operation rounded on its own and a correctly rounded root: a numpy float32 restatement gives the same
+ *                    bits.  An index outside [0,V) gives NaN and reads nothing.
+ * distances          d is the least fixpoint of d[s] = 0 at the sources and d[v] = min_u fl32(d[u] + length(u,v)); unreachable
+ *                    vertices hold +inf.  fl32(a + l) is monotone in a, so the fixpoint is unique and equals a heap Dijkstra
+ *                    with float32 additions bit for bit, whatever the order of the relaxations.
+ * labels             computed after d has converged, over the tight edges fl32(d[u] + length) == d[v] with d[v] finite:
+ *                    label[v] = the smallest position in the source list among the sources that reach v along tight edges (a
+ *                    source reaches itself; of a vertex listed twice the lower position counts); -1 where d = +inf.
+ * One workgroup of 1024 threads solves one problem and writes only that problem's outputs: no atomics, no communication
+ * between workgroups, the same bits on every run.  A range of at most fc_geodesic_lds_vertices vertices is solved in LDS (sized
+ * to the range), a larger one in the output row in global memory by the same loop.
+ * rows               S problems on one mesh, problem k with the single source sources[k]: dist (S,V).
+ * nearest            B problems: mesh b owns the vertices pos_ptr[b] .. pos_ptr[b+1] - 1 and the sources (vertex numbers of
+ *                    the union) at the positions src_ptr[b] .. src_ptr[b+1] - 1 of the list; both tables (B+1) int64 in DEVICE
+ *                    memory, checked by the CALLER, or both null for one mesh (B = 1, max_range = V).  dist (V), label (V)
+ *                    int64 positions in the whole list.  max_range: the largest range, at least every range's size (a larger
+ *                    range would be left unsolved).  The kernels clamp what they read from the tables and skip sources and
+ *                    neighbours outside the problem's range: malformed input gives a meaningless result, no access outside
+ *                    the buffers.
+ * sweeps             null, or int32 (problems,2): the sweeps of the distance loop and of the label loop (the last one of each
+ *                    changes nothing).
+ * Workspace (nearest only): the query below, 4 V bytes when max_range exceeds the LDS capacity, else 0; FC_ERR_WORKSPACE when
+ * missing or smaller.  V, E < 2^31.  No allocation or synchronisation inside.
+ * face areas         area[f] = 0.5 |(b - a) x (c - a)| for face (3,F) int64, float32, each operation rounded on its own; NaN for
+ *                    an index outside [0,V).
+ * segment sum        out[k] = (x[ptr[k]] + ... + x[ptr[k+1] - 1]) / divisor, added in float32 from left to right, one rounded
+ *                    division (ptr (K+1) int64 in device memory, clamped to [0,N]): the fixed-order sum under the lumped
+ *                    vertex masses (divisor 3) and the sample weights (divisor 1). */
+int32_t fc_geodesic_lds_vertices(void);
+int fc_mesh_edge_lengths(const float* pos, const int32_t* src, const int32_t* nbr, int32_t V, int32_t E, float* length, void* stream);
+int fc_geodesic_rows(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* sources, int32_t S,
+                     float* dist, int32_t* sweeps, void* stream);
+size_t fc_geodesic_workspace_bytes(int32_t V, int32_t max_range);
+int fc_geodesic_nearest(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                        const int64_t* sources, const int64_t* src_ptr, int32_t S, int32_t B, int32_t max_range, float* dist,
+                        int64_t* label, int32_t* sweeps, void* workspace, size_t workspace_bytes, void* stream);
+int fc_face_areas(const float* pos, const int64_t* face, int32_t V, int32_t F, float* area, void* stream);
+int fc_segment_sum_f32(const float* x, const int64_t* ptr, int64_t N, int32_t K, float divisor, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
