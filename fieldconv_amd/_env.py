@@ -18,6 +18,7 @@ SWITCHES = {
     'FC_RING_HALVES': '0: no half tiles in the last round of the ring-major forward kernel',
     'FC_HALF_TILES': '0: no half tiles in the frequency-major kernels; 2: half tiles in the backward kernels too',
     'FC_BWD_STREAM': '0: the data / filter kernel pair on large meshes too, instead of the H-streaming arrangement (gather + stream + gx kernels)',
+    'FC_GATHER_WPG': '16 / 4: the gather kernel of the H-streaming arrangement as one 16-wavefront workgroup per CU / as five 4-wavefront ones, whatever its registers say',
     'FC_FILTER2': '0: the LDS-staged half-precision filter-gradient kernel instead of the register-fed one',
     'FC_SPLIT_FINISH': '1: partial sums and parameter-gradient chain as two launches',
     'FC_EDGE_PARTS_MAX': 'cap (log2) on the number of workgroups that share a tile on small meshes',
@@ -63,7 +64,7 @@ TEST_SWITCHES = {
 }
 
 # the switches that exist in the development build of the library only (csrc: dev_env under -DFC_DEV_SWITCHES)
-LIBRARY_SWITCHES = ('FC_BWD_STREAM', 'FC_RING', 'FC_GROUP_SPLIT', 'FC_RING_COMPACT', 'FC_RING_HALVES', 'FC_HALF_TILES', 'FC_FILTER2', 'FC_SPLIT_FINISH',
+LIBRARY_SWITCHES = ('FC_BWD_STREAM', 'FC_GATHER_WPG', 'FC_RING', 'FC_GROUP_SPLIT', 'FC_RING_COMPACT', 'FC_RING_HALVES', 'FC_HALF_TILES', 'FC_FILTER2', 'FC_SPLIT_FINISH',
                     'FC_EDGE_PARTS_MAX', 'FC_ECHO_WPV', 'FC_STAMP_KERNEL', 'FC_DEBUG', 'FC_DEBUG_BWD', 'FC_DEBUG_RP', 'FC_DEBUG_RG', 'FC_LIN_DIRECT')
 
 PREFIXES = ('FC_', 'FIELDCONV_', 'BENCH_')

@@ -611,10 +611,14 @@ __global__ void fc_reduce_gw_kernel(const float2* __restrict__ gwp, float2* __re
 template <int R, int B>
 static int launch_gather(const float2* gy, const float* rec, const fc_csr* g, const float* wpk, char* hrec, const StreamArgs& a,
                          const StreamPlan& p, hipStream_t stream) {
-    auto kern = fc_backward_gather_kernel<R, B>;
-    const size_t lds = (size_t)kWaves * kRingChunks * 1024;
-    const int grid = p.ntiles < num_cus() ? p.ntiles : num_cus();
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, gy, rec, g->rowptr, g->runs, wpk, hrec, a);
+    // (plan_gather: five 4-wavefront workgroups per CU where the instantiation fits 96 registers, else one 16-wavefront workgroup)
+    const size_t lds = (size_t)p.gwpg * kRingChunks * 1024;         // one record ring per wavefront
+    if (p.gwpg == kGatherSmallWaves)
+        hipLaunchKernelGGL((fc_backward_gather_kernel<R, B, kGatherSmallWaves, kGatherSmallResidency>), dim3(p.ggrid), dim3(kGatherSmallWaves * kWave),
+                           lds, stream, gy, rec, g->rowptr, g->runs, wpk, hrec, a);
+    else
+        hipLaunchKernelGGL((fc_backward_gather_kernel<R, B, kWaves, kWaves / 4>), dim3(p.ggrid), dim3(kThreads), lds, stream, gy, rec, g->rowptr,
+                           g->runs, wpk, hrec, a);
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
@@ -734,10 +738,10 @@ void describe_backward(const fc_dims* d, int records, char* buf, size_t n) {
     {
         const StreamPlan sp = plan_stream(d, halves_of(d), records != 0);
         if (sp.ok) {
-            snprintf(buf, n, "fc_backward_gather_kernel<records,split-f16> tiles=%d; fc_backward_stream_kernel (H once for gxt and gW: %d gxt + %d gW "
+            snprintf(buf, n, "fc_backward_gather_kernel<records,split-f16> tiles=%d (%d workgroups of %d wavefronts, %d per SIMD); fc_backward_stream_kernel (H once for gxt and gW: %d gxt + %d gW "
                      "wavefronts, W_f in registers, records by LDS-DMA) grid=%dx%d; fc_backward_gx_kernel; module parameters: "
                      "fc_backward_finish_params (sum of the partials + parameter chain) in one launch; explicit filter: fc_backward_finish; cus=%d",
-                     sp.ntiles, sp.G, sp.NW, sp.P, sp.FS, num_cus());
+                     sp.ntiles, sp.ggrid, sp.gwpg, sp.gwaves, sp.G, sp.NW, sp.P, sp.FS, num_cus());
             return;
         }
     }

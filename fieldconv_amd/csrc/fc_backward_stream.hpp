@@ -35,6 +35,8 @@ struct StreamPlan {
     int KS;              // slices per frequency: the o-major k range in one piece or in two halves (lanes [0, O/2) | [O/2, O) of the gather)
     int FS, KPS;         // F * KS slices of KPS = KP / KS entries: what one workgroup of the streaming kernel takes (KST, KSI, NU, G, NW, T: per slice)
     int NG;              // walks per vertex of the gather kernel (at most 32 ring x frequency sums per lane and walk)
+    int gwpg, gwaves;    // the gather launch: wavefronts per workgroup (= vertices per work item) and wavefronts per SIMD (plan_gather)
+    int ggrid;           // its persistent grid
     int img_bytes;       // 16 * KSI halves
     int rec_bytes;       // image + [16] s_v + [16] 1/s_v, rounded up to whole KiB (DMA pieces)
     size_t lds;
@@ -58,6 +60,10 @@ struct StreamArgs {
 // The arrangement serves meshes that fill the machine for several rounds, in the default arithmetic mode, on shapes whose
 // registers and LDS it fits (the reference's default layer -- 48 channels, 6 rings, band limit 2 -- among them); everything
 // else keeps the data / filter kernel pair.
+constexpr int kGatherSmallWaves = 4;      // the gather kernel's small workgroup: 4 wavefronts, one per SIMD ...
+constexpr int kGatherSmallResidency = 5;  // ... five of them on a CU where the instantiation fits (512 / 5 -> 96 registers)
+inline void plan_gather(const fc_dims* d, StreamPlan& p);      // (behind the kernel: it asks for the instantiation's compiled resources)
+
 inline StreamPlan plan_stream(const fc_dims* d, int halves, bool factored) {
     StreamPlan p = {};
     p.ok = false;
@@ -114,6 +120,7 @@ inline StreamPlan plan_stream(const fc_dims* d, int halves, bool factored) {
     p.gxt_bytes = (size_t)p.FS * d->N * I * sizeof(float2);
     p.wst_bytes = (size_t)p.FS * p.G * 4 * kStreamUnits * kWave * 16;     // the gxt wavefronts' filter fragments, in the order they load them
     p.nt_dump = p.hrec_bytes > ((size_t)192 << 20) ? 1 : 0;
+    plan_gather(d, p);
     p.ok = true;
     return p;
 }
@@ -158,8 +165,13 @@ __device__ __forceinline__ void store_plane_row(uint32_t* dst, const uint32_t (&
 }
 
 // ------------------------------------------------------------------------------------------------ gather
-template <int R, int B>
-__global__ __launch_bounds__(kThreads) void fc_backward_gather_kernel(
+// WPG wavefronts per workgroup (a divisor of 16), MINW wavefronts per SIMD the register budget is held to.  The work item is a GROUP
+// of WPG consecutive vertices, wavefront w of it walks vertex item * WPG + w; the record address follows from the vertex (tile
+// j >> 4, row j & 15), so 16 / WPG items fill a tile's records exactly as one 16-wavefront workgroup does.  <16, 4> is the geometry
+// the kernel was built with (a 128-register budget); <4, 5> lets five 256-thread workgroups share a CU where the instantiation fits
+// 96 registers without scratch (gather_geometry).
+template <int R, int B, int WPG, int MINW>
+__global__ __launch_bounds__(WPG * kWave, MINW) void fc_backward_gather_kernel(
     const float2* __restrict__ ggy, const float* __restrict__ gsten, const int32_t* __restrict__ growptr,
     const int32_t* __restrict__ gruns, const float* __restrict__ gwpk, char* __restrict__ hrec, const StreamArgs a) {
     constexpr int F = 2 * B + 1;
@@ -179,16 +191,19 @@ __global__ __launch_bounds__(kThreads) void fc_backward_gather_kernel(
     const int ol = lane < O ? lane : 0;       // lanes >= O gather channel 0 and are never stored
 
     auto dma_chunk = [&](const int first, const int ch) {
-        const float* src = gsten + ((size_t)first + ((size_t)ch << LOG_CR)) * RECF + lane * 4;
+        // (wave-uniform chunk address + a 32-bit lane offset formed on the spot: no 64-bit pointer per lane kept alive across the walk)
+        uint32_t lane_off = lane;
+        asm volatile("" : "+v"(lane_off));
+        const char* src = reinterpret_cast<const char*>(gsten + ((size_t)first + ((size_t)ch << LOG_CR)) * RECF) + lane_off * 16u;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(ring + (ch & (NR - 1)) * 256), 16, 0, 0);
     };
-    auto slot_range = [&](const int tile, int& b, int& e, int (&run)[R]) {
+    auto slot_range = [&](const int item, int& b, int& e, int (&run)[R]) {
         b = 0;
         e = 0;
 #pragma unroll
         for (int q = 0; q < R; ++q) run[q] = 0;
-        const int j = tile * kTile + wave;
-        if (tile < a.ntiles && j < a.N) {
+        const int j = item * WPG + wave;         // (items past the last one start at or behind ntiles * 16 >= N)
+        if (j < a.N) {
             b = growptr[j];
             e = growptr[j + 1];
 #pragma unroll
@@ -200,7 +215,8 @@ __global__ __launch_bounds__(kThreads) void fc_backward_gather_kernel(
         else return ring + ((s >> LOG_CR) & (NR - 1)) * 256 + (s & (CR - 1)) * RECF;
     };
 
-    const int grid = gridDim.x;
+    static_assert(kTile % WPG == 0, "whole groups per tile");
+    const int grid = gridDim.x, nitems = a.ntiles * (kTile / WPG);      // (whole tiles: the rows behind vertex N - 1 are stored as zeros)
     int beg = 0, end = 0, ro[R];
     {
         slot_range(first_tile_of_block(), beg, end, ro);
@@ -210,15 +226,13 @@ __global__ __launch_bounds__(kThreads) void fc_backward_gather_kernel(
     // lanes of a vertex's row: output channel o = lane; with two slices per frequency the lanes [0, O/2) and [O/2, O) store into the
     // records of the first and of the second half of the o-major k range
     const int OH = O / a.KS;
-    const int half = (lane >= OH && a.KS == 2) ? 1 : 0;
-    const int lane_in_half = lane - half * OH;
-    for (int tile = first_tile_of_block(); tile < a.ntiles; tile += grid) {
+    for (int item = first_tile_of_block(); item < nitems; item += grid) {
         int nbeg = 0, nend = 0, nro[R];
-        slot_range(tile + grid, nbeg, nend, nro);
+        slot_range(item + grid, nbeg, nend, nro);
+        const int j = item * WPG + wave, tile = j >> 4, row = j & (kTile - 1);        // my vertex: its tile's records, its row in them
         const int nslots = end - beg;
         const int nch = (nslots + CR - 1) >> LOG_CR;
         char* const rec0 = hrec + (size_t)tile * a.F * a.rec_bytes;          // (a.F: slices per tile)
-        const int row_off = wave * a.KSI * 2 + lane_in_half * R * 2;         // bytes: my vertex's row, my R entries of a plane
 
         // one walk per group of NF frequencies [F0, F0 + NF): at most 32 ring x frequency sums per lane and walk
         static_for<0, NG>([&](auto gc) {
@@ -309,6 +323,15 @@ __global__ __launch_bounds__(kThreads) void fc_backward_gather_kernel(
             float scale, inv_scale;
             split_scale(mx, scale, inv_scale);
             if (mx == 0.f) inv_scale = 0.f;           // an all-zero row drops out of the second operand x~ / s_v and its column scales
+            // bytes from the record of slice (frequency, first half): my half's record, my vertex's row, my R entries of a plane -- 32-bit
+            // offsets formed here, from the lane number, beside wave-uniform record addresses (kept across the walk as 64-bit addresses per
+            // frequency and lane they are ten registers)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int half = (ln >= OH && a.KS == 2) ? 1 : 0;
+            const int lane_in_half = ln - half * OH;
+            const uint32_t half_off = (uint32_t)half * (uint32_t)a.rec_bytes;
+            const uint32_t row_off = half_off + (uint32_t)(row * a.KSI * 2 + lane_in_half * R * 2);
             auto rows = [&](auto nt_c) {
                 constexpr bool NT = decltype(nt_c)::value;
 #pragma unroll
@@ -330,18 +353,18 @@ __global__ __launch_bounds__(kThreads) void fc_backward_gather_kernel(
                         p2[dd] = __builtin_amdgcn_perm(hi[2 * dd + 1], hi[2 * dd], kHigh);      // im_hi
                         p3[dd] = __builtin_amdgcn_perm(lo[2 * dd + 1], lo[2 * dd], kHigh);      // im_lo
                     }
-                    char* const recf = rec0 + (size_t)((F0 + f) * a.KS + half) * a.rec_bytes;     // the record of slice (frequency, my half)
-                    if (lane < O && !(kDevSwitches && (a.dbg & 8))) {
+                    char* const recf = rec0 + (size_t)((F0 + f) * a.KS) * a.rec_bytes;     // the record of slice (frequency, first half)
+                    if (ln < O && !(kDevSwitches && (a.dbg & 8))) {
                         char* const dst = recf + row_off;
                         store_plane_row<R, NT>(reinterpret_cast<uint32_t*>(dst), p0);
                         store_plane_row<R, NT>(reinterpret_cast<uint32_t*>(dst + a.KP * 2), p1);
                         store_plane_row<R, NT>(reinterpret_cast<uint32_t*>(dst + a.KP * 4), p2);
                         store_plane_row<R, NT>(reinterpret_cast<uint32_t*>(dst + a.KP * 6), p3);
                     }
-                    if (lane_in_half == 0 && lane < O) {
-                        float* tail = reinterpret_cast<float*>(recf + a.img_bytes);
-                        tail[wave] = scale;
-                        tail[kTile + wave] = inv_scale;
+                    if (lane_in_half == 0 && ln < O) {
+                        float* tail = reinterpret_cast<float*>(recf + half_off + (uint32_t)a.img_bytes);
+                        tail[row] = scale;
+                        tail[kTile + row] = inv_scale;
                     }
                 }
             };
@@ -364,7 +387,7 @@ __global__ __launch_bounds__(kThreads) void fc_backward_gather_kernel(
         const int NU = a.NMT * a.KST;
         const size_t plane_sz = (size_t)a.IP * a.wKP;                               // halves per plane
         const uint16_t* const img0 = reinterpret_cast<const uint16_t*>(gwpk + a.IP);
-        for (int e = blockIdx.x * kThreads + tid; e < total; e += gridDim.x * kThreads) {
+        for (int e = (blockIdx.x * WPG + wave) * kWave + lane; e < total; e += gridDim.x * (WPG * kWave)) {
             const int ln = e & 63, pl = (e >> 6) & 3, ui = (e >> 8) % kStreamUnits, fg = e / (kStreamUnits * 4 * kWave);
             const int g_ = fg % a.G, sl = fg / a.G;              // slice = (frequency, half of the k range)
             const int f_ = sl / a.KS, k0 = (sl - f_ * a.KS) * a.KP;
@@ -389,6 +412,41 @@ __global__ __launch_bounds__(kThreads) void fc_backward_gather_kernel(
             *reinterpret_cast<u32x4*>(a.wst + (size_t)e * 4) = u32x4{v[0], v[1], v[2], v[3]};
         }
     }
+}
+
+// Geometry of the gather launch, per instantiation, from what the compiler made of it.  The walk is bound by the latency of its row
+// requests and record reads, which a fifth wavefront per SIMD helps to hide; the register file gives one only to a kernel of at most
+// 96 registers, and only in workgroups small enough to leave none of the 20 places of a CU empty.  The small-workgroup instantiation
+// is compiled under that budget; where it met it WITHOUT scratch (a reload behind a row request waits for the request) it is
+// taken, everything else keeps one 16-wavefront workgroup per CU.  FC_GATHER_WPG=16 / 4 (development) forces either.
+template <int R, int B>
+inline bool gather_fits_small() {
+    static const bool fits = [] {
+        hipFuncAttributes at;
+        const void* fn = reinterpret_cast<const void*>(fc_backward_gather_kernel<R, B, kGatherSmallWaves, kGatherSmallResidency>);
+        if (hipFuncGetAttributes(&at, fn) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        return at.localSizeBytes == 0 && at.numRegs <= (512 / kGatherSmallResidency) / 8 * 8;
+    }();
+    return fits;
+}
+
+inline void plan_gather(const fc_dims* d, StreamPlan& p) {
+    bool small = false;
+#define FC_GATHER_CASE(RR, BB) if (d->R == RR && d->B == BB) small = gather_fits_small<RR, BB>();
+    FC_GATHER_CASE(2, 1) FC_GATHER_CASE(4, 1) FC_GATHER_CASE(6, 1) FC_GATHER_CASE(8, 1)
+    FC_GATHER_CASE(2, 2) FC_GATHER_CASE(4, 2) FC_GATHER_CASE(6, 2) FC_GATHER_CASE(8, 2)
+    FC_GATHER_CASE(2, 3) FC_GATHER_CASE(4, 3) FC_GATHER_CASE(6, 3) FC_GATHER_CASE(8, 3)
+#undef FC_GATHER_CASE
+    static const int forced = [] { const char* e = dev_env("FC_GATHER_WPG"); return e ? atoi(e) : 0; }();
+    if (forced == kWaves) small = false;
+    if (forced == kGatherSmallWaves) small = true;
+    p.gwpg = small ? kGatherSmallWaves : kWaves;
+    p.gwaves = small ? kGatherSmallResidency : kWaves / 4;
+    const int nitems = p.ntiles * (kTile / p.gwpg), places = num_cus() * (small ? kGatherSmallResidency : 1);
+    p.ggrid = nitems < places ? nitems : places;
 }
 
 // ------------------------------------------------------------------------------------------------ stream
