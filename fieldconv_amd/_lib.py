@@ -214,6 +214,15 @@ SIGNATURES = {
                                            _sz, _vp]),
     'fc_face_areas': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp]),
     'fc_segment_sum_f32': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _c_int32, ctypes.c_float, _vp, _vp]),
+    'fc_geodesic_fps_lds_vertices': (_c_int32, []),
+    'fc_geodesic_fps_workspace_bytes': (_sz, [_c_int32, _c_int32]),
+    'fc_geodesic_fps': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _c_int32, _c_int32, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp,
+                                       _vp, _sz, _vp]),
+    'fc_geodesic_ball_workspace_bytes': (_sz, [_c_int32, _c_int32]),
+    'fc_geodesic_ball_count': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _vp, _c_int32, _c_int32, _vp, _c_int32, _c_int32, _c_int32,
+                                              ctypes.c_float, _c_int32, _vp, _vp, _sz, _vp]),
+    'fc_geodesic_ball_fill': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _vp, _c_int32, _c_int32, _vp, _c_int32, _c_int32, _c_int32,
+                                             ctypes.c_float, _c_int32, _vp, ctypes.c_int64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _LIB = None

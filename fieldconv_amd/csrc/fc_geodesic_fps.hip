@@ -1,0 +1,433 @@
+// Sampling and neighbourhoods by the edge-graph metric of fc_geodesic.hip (same CSR, same float32 lengths, same fixpoint):
+//   fc_geodesic_fps              farthest-point sampling: per mesh, n_samples rounds of (argmax of the field over the vertices not
+//                                yet taken, d[new] = 0, relaxation to the new fixpoint) inside ONE launch, one workgroup per mesh;
+//   fc_geodesic_ball_count/fill  one workgroup per query sample: the single-source field bounded by epsilon, then the samples of
+//                                the query's mesh with d < epsilon as rows [query, position], at most K nearest of them.
+// Both rest on one relaxation loop (gf_relax).  A workgroup of 1024 threads owns one problem; thread t owns the vertices
+// t, t + 1024, ... of its range and is the only writer of their distances.  A vertex is pulled only while its dirty flag is set.
+// Flags are double-buffered: in a sweep the owner reads and clears cur[v]; a vertex whose distance drops sets nxt[u] = 1 on all
+// its neighbours; the buffers swap at the barrier.  Why the result is the least fixpoint whatever the schedule: every value ever
+// written is the rounded length of a path from a source (an upper bound of the fixpoint, fl32(a + l) being monotone in a), and
+// take the LAST pull of v, in sweep s: it left d[v] <= fl32(d_read[u] + len) for every neighbour u.  If d[u] dropped at or after
+// that read, in a sweep s' >= s, then u set nxt[v] in s' and v was pulled again in s' + 1 > s, so it was not the last pull: on
+// every edge d[v] <= fl32(d[u] + len) holds at the end, and that state is the fixpoint (header of fc_geodesic.hip).  Nothing in
+// this needs an order between a thread's accesses inside a sweep; only the barrier orders.  A flag byte is written with the
+// value it is meant to have by whoever writes it (cur: 0 by the owner; nxt: 1 by anyone), so concurrent stores agree.
+// The incremental start of a round is legitimate for the same reason: after d[new] = 0 the state is pointwise an upper bound of
+// the new fixpoint, and only the neighbours of `new` can violate their edge condition: they are the ones flagged.
+// The bounded field of a ball accepts a candidate only if it is < epsilon; a prefix of a shortest path is never longer than the
+// path (float32 additions of non-negative lengths are monotone), so it equals the unbounded field wherever that is < epsilon.
+// Loops are bounded by the problem: a relaxation runs at most n + 1 sweeps, a mesh exactly n_samples rounds.  No atomics.
+#include <limits.h>
+#include "../../include/fieldconv_hip.h"
+#include "fc_common.hpp"
+#include "fc_kernels.hpp"
+
+namespace fc {
+
+constexpr int kGfThreads = 1024;
+constexpr int kGfWaves = kGfThreads / 64;
+// Vertices of a range solved in LDS.  Sampling keeps 7 B per vertex (distance, two dirty buffers, taken), a ball 6 B:
+// 140 000 B of the CU's 163 840, beside the static scratch of the workgroup reductions.
+constexpr int kGfLdsVertices = 20000;
+
+struct gf_graph {
+    const int32_t* rowptr;       // (V+1) CSR over the vertices of all meshes
+    const int32_t* nbr;          // (E)
+    const float* len;            // (E)
+    int32_t V, E;
+};
+
+__device__ __forceinline__ int64_t gf_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the neighbours of local vertex i (inside the range) get flag[u] = 1; the whole workgroup shares the row
+__device__ __forceinline__ void gf_flag_neighbours(const gf_graph& g, int v0, int n, int i, uint8_t* flag, int t) {
+    const int e0 = max(g.rowptr[v0 + i], 0), e1 = min(g.rowptr[v0 + i + 1], g.E);
+    for (int e = e0 + t; e < e1; e += kGfThreads) {
+        const int u = g.nbr[e] - v0;
+        if ((unsigned)u < (unsigned)n) flag[u] = 1;
+    }
+}
+
+// Pull-relaxation of the flagged vertices to the fixpoint (see the header).  Called by the whole workgroup after a barrier; every
+// sweep ends in one, the last included.  Candidates must be < bound (+inf: no bound).  Returns the sweeps; the last changes nothing.
+__device__ __forceinline__ int gf_relax(const gf_graph& g, int v0, int n, float* d, uint8_t*& cur, uint8_t*& nxt, float bound, int t) {
+    int sw = 0;
+    for (;;) {
+        int changed = 0;
+        for (int i = t; i < n; i += kGfThreads) {
+            if (!cur[i]) continue;
+            cur[i] = 0;
+            const int e0 = max(g.rowptr[v0 + i], 0), e1 = min(g.rowptr[v0 + i + 1], g.E);
+            const float old = d[i];
+            float best = old;
+            for (int e = e0; e < e1; ++e) {
+                const int u = g.nbr[e] - v0;
+                if ((unsigned)u < (unsigned)n) {
+                    const float c = d[u] + g.len[e];
+                    best = (c < best && c < bound) ? c : best;
+                }
+            }
+            if (best < old) {
+                d[i] = best;
+                changed = 1;
+                for (int e = e0; e < e1; ++e) {
+                    const int u = g.nbr[e] - v0;
+                    if ((unsigned)u < (unsigned)n) nxt[u] = 1;
+                }
+            }
+        }
+        ++sw;
+        uint8_t* const s = cur;
+        cur = nxt, nxt = s;
+        if (!__syncthreads_or(changed) || sw > n) break;
+    }
+    return sw;
+}
+
+// ------------------------------------------------------------------------------------------------ farthest-point sampling
+struct gfps_args {
+    gf_graph g;
+    const int64_t* pos_ptr;      // null: one mesh spanning [0,V); else mesh p spans [pos_ptr[p], pos_ptr[p+1])
+    const int64_t* n_samples;    // (B) rounds of mesh p
+    const int64_t* start;        // (B) first sample, local to the mesh
+    const int64_t* out_ptr;      // (B) where mesh p's indices begin in idx
+    int64_t total_out;
+    int64_t* idx;                // (total_out) local indices in selection order
+    float* dist;                 // (V) the final field of every mesh
+    int64_t* sweeps;             // null, or (B) relaxation sweeps summed over the rounds
+    uint8_t* ws;                 // (3 V) flags of the ranges that do not fit LDS
+    int32_t lds_vertices;        // ranges of at most this many vertices belong to the LDS instantiation, larger ones to the other
+};
+
+template <bool kLds>
+__global__ __launch_bounds__(kGfThreads) void geodesic_fps_kernel(const gfps_args a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ unsigned long long s_key[kGfWaves];
+    const int p = blockIdx.x, t = threadIdx.x;
+    // whatever the tables hold, a mesh reads and writes inside [0,V) and its own slots of idx only
+    int v0 = 0, v1 = a.g.V;
+    if (a.pos_ptr) {
+        v0 = (int)gf_clamp(a.pos_ptr[p], 0, a.g.V);
+        v1 = (int)gf_clamp(a.pos_ptr[p + 1], v0, a.g.V);
+    }
+    const int n = v1 - v0;
+    if ((n <= a.lds_vertices) != kLds || n < 1) return;          // (uniform over the workgroup)
+    const int64_t o0 = gf_clamp(a.out_ptr[p], 0, a.total_out);
+    const int64_t rounds = gf_clamp(a.n_samples[p], 0, min((int64_t)n, a.total_out - o0));
+    const int first = (int)gf_clamp(a.start[p], 0, n - 1);
+    float* const row = a.dist + v0;
+    float* const d = kLds ? reinterpret_cast<float*>(smem) : row;
+    uint8_t* const flags = kLds ? reinterpret_cast<uint8_t*>(smem) + 4 * (size_t)a.lds_vertices : nullptr;
+    uint8_t* cur = kLds ? flags : a.ws + v0;
+    uint8_t* nxt = kLds ? flags + a.lds_vertices : a.ws + (size_t)a.g.V + v0;
+    uint8_t* const taken = kLds ? flags + 2 * (size_t)a.lds_vertices : a.ws + 2 * (size_t)a.g.V + v0;
+    const float inf = __int_as_float(0x7f800000);
+
+    for (int i = t; i < n; i += kGfThreads) {
+        d[i] = inf;
+        cur[i] = 0, nxt[i] = 0, taken[i] = 0;
+    }
+    __syncthreads();
+
+    int64_t sweeps = 0;
+    for (int64_t k = 0; k < rounds; ++k) {
+        int pick = first;
+        if (k > 0) {
+            // largest d, then lowest vertex: d >= 0 or +inf, so its bits order as an unsigned integer
+            unsigned long long key = 0;
+            for (int i = t; i < n; i += kGfThreads) {
+                if (taken[i]) continue;
+                const unsigned long long c = ((unsigned long long)__float_as_uint(d[i]) << 32) | (0xffffffffu - (unsigned)i);
+                key = c > key ? c : key;
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long c = __shfl_xor(key, o);
+                key = c > key ? c : key;
+            }
+            if ((t & 63) == 0) s_key[t >> 6] = key;
+            __syncthreads();
+            key = 0;
+            for (int w = 0; w < kGfWaves; ++w) key = s_key[w] > key ? s_key[w] : key;
+            __syncthreads();          // (s_key is written again in the next round)
+            pick = (int)gf_clamp((int64_t)(0xffffffffu - (unsigned)(key & 0xffffffffu)), 0, n - 1);          // (rounds <= n: one is left)
+        }
+        if (t == 0) {
+            taken[pick] = 1;
+            d[pick] = 0.f;
+            a.idx[o0 + k] = pick;
+        }
+        gf_flag_neighbours(a.g, v0, n, pick, cur, t);
+        __syncthreads();
+        sweeps += gf_relax(a.g, v0, n, d, cur, nxt, inf, t);
+    }
+    if (kLds)
+        for (int i = t; i < n; i += kGfThreads) row[i] = d[i];
+    if (t == 0 && a.sweeps) a.sweeps[p] = sweeps;
+}
+
+// ------------------------------------------------------------------------------------------------ geodesic balls
+struct gball_args {
+    gf_graph g;
+    const int64_t* pos_ptr;      // both null: one mesh, every sample; else (B+1) ranges of the vertices and of the sample positions
+    const int64_t* smp_ptr;
+    int32_t B;
+    const int64_t* sample_idx;   // (S) vertex numbers
+    int32_t S;
+    int32_t q0;                  // workgroup w solves query q0 + w
+    float eps;
+    int32_t K;
+    int32_t* count;              // (S) min(in-ball samples, K) of every query: written by the counting launch
+    const int64_t* off;          // (S+1) where every query's rows begin: read by the filling launch
+    int64_t n_edges;
+    int64_t* edges;              // (n_edges, 2)
+    float* edge_dist;            // null, or (n_edges)
+    uint8_t* ws;                 // slot w of the ranges that do not fit LDS: 4 n bytes of distances, then 2 n of flags
+    size_t ws_stride;
+    int32_t lds_vertices;
+    int32_t max_range;           // what a workspace slot was sized for: a larger range is left unsolved
+};
+
+// exclusive prefix of pred over the workgroup (thread order) and the total; two barriers
+__device__ __forceinline__ int gf_scan(bool pred, int t, int* s_wave, int& total) {
+    const unsigned long long b = __ballot(pred);
+    const int lane = t & 63, w = t >> 6;
+    const int before = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) s_wave[w] = __popcll(b);
+    __syncthreads();
+    int below = 0;
+    total = 0;
+    for (int i = 0; i < kGfWaves; ++i) {
+        const int c = s_wave[i];
+        below += i < w ? c : 0;
+        total += c;
+    }
+    __syncthreads();
+    return below + before;
+}
+
+template <bool kLds, bool kFill>
+__global__ __launch_bounds__(kGfThreads) void geodesic_ball_kernel(const gball_args a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_wave[kGfWaves];
+    const int t = threadIdx.x;
+    const int q = a.q0 + (int)blockIdx.x;
+    if (q < 0 || q >= a.S) return;
+    int v0 = 0, v1 = a.g.V, s0 = 0, s1 = a.S;
+    if (a.pos_ptr) {
+        int lo = 0, hi = a.B - 1;          // the last mesh whose sample range begins at or before q
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (a.smp_ptr[mid] <= q) lo = mid; else hi = mid - 1;
+        }
+        v0 = (int)gf_clamp(a.pos_ptr[lo], 0, a.g.V);
+        v1 = (int)gf_clamp(a.pos_ptr[lo + 1], v0, a.g.V);
+        s0 = (int)gf_clamp(a.smp_ptr[lo], 0, a.S);
+        s1 = (int)gf_clamp(a.smp_ptr[lo + 1], s0, a.S);
+    }
+    const int n = v1 - v0;
+    if ((n <= a.lds_vertices) != kLds || n > a.max_range) return;          // (uniform over the workgroup)
+    uint8_t* const slot = kLds ? reinterpret_cast<uint8_t*>(smem) : a.ws + a.ws_stride * blockIdx.x;
+    const int cap = kLds ? a.lds_vertices : n;
+    float* const d = reinterpret_cast<float*>(slot);
+    uint8_t* cur = slot + 4 * (size_t)cap;
+    uint8_t* nxt = cur + cap;
+    const float inf = __int_as_float(0x7f800000);
+
+    for (int i = t; i < n; i += kGfThreads) {
+        d[i] = inf;
+        cur[i] = 0, nxt[i] = 0;
+    }
+    __syncthreads();
+    const int64_t src = a.sample_idx[q] - v0;
+    if (src >= 0 && src < n) {
+        if (t == 0) d[src] = 0.f;
+        gf_flag_neighbours(a.g, v0, n, (int)src, cur, t);
+        __syncthreads();
+        gf_relax(a.g, v0, n, d, cur, nxt, a.eps, t);
+    }
+
+    // the samples of this mesh inside the ball: d < eps (the source holds 0, every other finite value passed the bound)
+    auto key_of = [&](int j, unsigned long long& key) -> bool {
+        if (j >= s1) return false;
+        const int64_t v = a.sample_idx[j] - v0;
+        if (v < 0 || v >= n) return false;
+        const float dv = d[v];
+        key = ((unsigned long long)__float_as_uint(dv) << 32) | (unsigned)j;          // (distance, position)
+        return dv < a.eps;
+    };
+    int found = 0;
+    for (int base = s0; base < s1; base += kGfThreads) {
+        unsigned long long key = 0;
+        found += __syncthreads_count(key_of(base + t, key));
+    }
+    const int keep = min(found, a.K);
+    if (!kFill) {
+        if (t == 0) a.count[q] = keep;
+        return;
+    }
+    // more than K: the K-th smallest key, bit by bit from the top (keys are distinct, so exactly K keys are <= it)
+    unsigned long long limit = ~0ull;
+    if (found > a.K) {
+        limit = 0;
+        for (int bit = 63; bit >= 0; --bit) {
+            const unsigned long long trial = limit | ((1ull << bit) - 1ull);          // this bit 0, every lower bit 1
+            int below = 0;
+            for (int base = s0; base < s1; base += kGfThreads) {
+                unsigned long long key = 0;
+                const bool in = key_of(base + t, key);
+                below += __syncthreads_count(in && key <= trial);
+            }
+            if (below < a.K) limit |= 1ull << bit;
+        }
+    }
+    const int64_t o0 = gf_clamp(a.off[q], 0, a.n_edges), o1 = gf_clamp(a.off[q + 1], o0, a.n_edges);
+    int64_t at = o0;
+    for (int base = s0; base < s1; base += kGfThreads) {
+        unsigned long long key = 0;
+        const bool in = key_of(base + t, key) && key <= limit;
+        int total;
+        const int64_t mine = at + gf_scan(in, t, s_wave, total);
+        if (in && mine < o1) {
+            a.edges[2 * mine] = q;
+            a.edges[2 * mine + 1] = base + t;
+            if (a.edge_dist) a.edge_dist[mine] = __uint_as_float((unsigned)(key >> 32));
+        }
+        at += total;
+    }
+}
+
+}  // namespace fc
+
+namespace {
+
+bool gf_graph_ok(const int32_t* rowptr, const int32_t* nbr, const float* len, int32_t V, int32_t E) {
+    return rowptr && V >= 1 && E >= 0 && (E == 0 || (nbr && len));
+}
+
+// dynamic LDS above 64 KiB has to be allowed once per device and kernel
+int gf_allow_lds(const void* kernel, bool* done, size_t most) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= fc::kMaxDevices) return FC_ERR_LAUNCH;
+    if (!done[dev]) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess) return FC_ERR_LAUNCH;
+        done[dev] = true;
+    }
+    return FC_OK;
+}
+
+// the LDS share of a launch: ranges up to this size go to the LDS instantiation
+int32_t gf_lds_share(int32_t max_range, bool tables) { return max_range <= fc::kGfLdsVertices ? max_range : (tables ? fc::kGfLdsVertices : 0); }
+
+size_t gf_ball_stride(int32_t max_range) { return (6 * (size_t)max_range + 15) / 16 * 16; }
+
+template <bool kFill>
+int gf_ball_launch(fc::gball_args a, int32_t nq, int32_t max_range, hipStream_t s) {
+    static bool lds_ok[fc::kMaxDevices] = {};          // (per instantiation of this template: per kernel)
+    a.lds_vertices = gf_lds_share(max_range, a.pos_ptr != nullptr);
+    if (a.lds_vertices > 0) {
+        const size_t lds = 6 * (size_t)a.lds_vertices;
+        if (lds > 64 * 1024) {
+            const int st = gf_allow_lds(reinterpret_cast<const void*>(&fc::geodesic_ball_kernel<true, kFill>), lds_ok, 6 * (size_t)fc::kGfLdsVertices);
+            if (st != FC_OK) return st;
+        }
+        hipLaunchKernelGGL((fc::geodesic_ball_kernel<true, kFill>), dim3((unsigned)nq), dim3(fc::kGfThreads), lds, s, a);
+    }
+    if (max_range > fc::kGfLdsVertices)
+        hipLaunchKernelGGL((fc::geodesic_ball_kernel<false, kFill>), dim3((unsigned)nq), dim3(fc::kGfThreads), 0, s, a);
+    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+}
+
+bool gf_ball_args(fc::gball_args& a, const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                  const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S, int32_t q0, int32_t nq,
+                  float epsilon, int32_t K, void* workspace, size_t workspace_bytes, int* status) {
+    *status = FC_ERR_BAD_ARGUMENT;
+    if (!gf_graph_ok(rowptr, nbr, length, V, E) || S < 1 || B < 1 || !sample_idx || max_range < 0 || max_range > V || K < 1 || !(epsilon > 0.f))
+        return false;
+    if ((pos_ptr == nullptr) != (sample_ptr == nullptr) || (!pos_ptr && (B != 1 || max_range != V))) return false;
+    if (q0 < 0 || nq < 0 || (int64_t)q0 + nq > S) return false;
+    const size_t need = fc_geodesic_ball_workspace_bytes(max_range, nq);
+    if (need && (!workspace || workspace_bytes < need)) {
+        *status = FC_ERR_WORKSPACE;
+        return false;
+    }
+    a.g = {rowptr, nbr, length, V, E};
+    a.pos_ptr = pos_ptr, a.smp_ptr = sample_ptr, a.B = B;
+    a.sample_idx = sample_idx, a.S = S, a.q0 = q0, a.eps = epsilon, a.K = K;
+    a.ws = static_cast<uint8_t*>(workspace), a.ws_stride = gf_ball_stride(max_range), a.max_range = max_range;
+    *status = FC_OK;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t fc_geodesic_fps_lds_vertices(void) { return fc::kGfLdsVertices; }
+
+size_t fc_geodesic_fps_workspace_bytes(int32_t V, int32_t max_range) {
+    return V > 0 && max_range > fc::kGfLdsVertices ? 3 * (size_t)V : 0;
+}
+
+int fc_geodesic_fps(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr, int32_t B,
+                    int32_t max_range, const int64_t* n_samples, const int64_t* start, const int64_t* out_ptr, int64_t total_out,
+                    int64_t* idx, float* dist, int64_t* sweeps, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!gf_graph_ok(rowptr, nbr, length, V, E) || B < 1 || max_range < 0 || max_range > V || !n_samples || !start || !out_ptr ||
+        total_out < 1 || !idx || !dist)
+        return FC_ERR_BAD_ARGUMENT;
+    if (!pos_ptr && (B != 1 || max_range != V)) return FC_ERR_BAD_ARGUMENT;
+    const size_t need = fc_geodesic_fps_workspace_bytes(V, max_range);
+    if (need && (!workspace || workspace_bytes < need)) return FC_ERR_WORKSPACE;
+    static bool lds_ok[fc::kMaxDevices] = {};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    fc::gfps_args a = {};
+    a.g = {rowptr, nbr, length, V, E};
+    a.pos_ptr = pos_ptr, a.n_samples = n_samples, a.start = start, a.out_ptr = out_ptr, a.total_out = total_out;
+    a.idx = idx, a.dist = dist, a.sweeps = sweeps, a.ws = static_cast<uint8_t*>(workspace);
+    a.lds_vertices = gf_lds_share(max_range, pos_ptr != nullptr);
+    if (a.lds_vertices > 0) {
+        const size_t lds = 7 * (size_t)a.lds_vertices;
+        if (lds > 64 * 1024) {
+            const int st = gf_allow_lds(reinterpret_cast<const void*>(&fc::geodesic_fps_kernel<true>), lds_ok, 7 * (size_t)fc::kGfLdsVertices);
+            if (st != FC_OK) return st;
+        }
+        hipLaunchKernelGGL(fc::geodesic_fps_kernel<true>, dim3((unsigned)B), dim3(fc::kGfThreads), lds, s, a);
+    }
+    if (max_range > fc::kGfLdsVertices) hipLaunchKernelGGL(fc::geodesic_fps_kernel<false>, dim3((unsigned)B), dim3(fc::kGfThreads), 0, s, a);
+    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+}
+
+size_t fc_geodesic_ball_workspace_bytes(int32_t max_range, int32_t queries) {
+    return max_range > fc::kGfLdsVertices && queries > 0 ? gf_ball_stride(max_range) * (size_t)queries : 0;
+}
+
+int fc_geodesic_ball_count(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                           const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S, int32_t q0,
+                           int32_t nq, float epsilon, int32_t K, int32_t* count, void* workspace, size_t workspace_bytes, void* stream) {
+    fc::gball_args a = {};
+    int status;
+    if (!gf_ball_args(a, rowptr, nbr, length, V, E, pos_ptr, sample_ptr, B, max_range, sample_idx, S, q0, nq, epsilon, K, workspace,
+                      workspace_bytes, &status))
+        return status;
+    if (!count) return FC_ERR_BAD_ARGUMENT;
+    if (nq == 0) return FC_OK;
+    a.count = count;
+    return gf_ball_launch<false>(a, nq, max_range, static_cast<hipStream_t>(stream));
+}
+
+int fc_geodesic_ball_fill(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                          const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S, int32_t q0,
+                          int32_t nq, float epsilon, int32_t K, const int64_t* offsets, int64_t n_edges, int64_t* edges, float* edge_dist,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    fc::gball_args a = {};
+    int status;
+    if (!gf_ball_args(a, rowptr, nbr, length, V, E, pos_ptr, sample_ptr, B, max_range, sample_idx, S, q0, nq, epsilon, K, workspace,
+                      workspace_bytes, &status))
+        return status;
+    if (!offsets || n_edges < 0 || (n_edges > 0 && !edges)) return FC_ERR_BAD_ARGUMENT;
+    if (nq == 0 || n_edges == 0) return FC_OK;
+    a.off = offsets, a.n_edges = n_edges, a.edges = edges, a.edge_dist = edge_dist;
+    return gf_ball_launch<true>(a, nq, max_range, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -1209,3 +1209,5 @@ def trans_field(x, supp_edges, lift_sten, zonal_ang, zonal_mag, phase, ftype):
     return _TransFieldFn.apply(x, sten, stride, zonal_ang, zonal_mag, phase, csr, int(ftype))
 from .geodesic import (compose_map, correspondence_curve, geodesic_distances, geodesic_error, mesh_edge_graph, nearest_sample,          # noqa: E402,F401  (mesh geodesics: csrc/fc_geodesic.hip)
                        sample_weights, samples_to_nearest, vertex_masses)
+from .geodesic_sampling import (geodesic_farthest_point_sample, geodesic_farthest_point_sample_batched,          # noqa: E402,F401  (csrc/fc_geodesic_fps.hip)
+                                geodesic_radius_edges)

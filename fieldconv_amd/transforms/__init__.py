@@ -5,7 +5,10 @@ from .sample_weights import SampleWeights
 from .support_graph import (SupportGraph, farthest_point_sample, farthest_point_sample_batched, radius_edges,
                             radius_edges_batched)
 from ..geodesic import geodesic_distances, mesh_edge_graph, nearest_sample, sample_weights
+from ..geodesic_sampling import (geodesic_farthest_point_sample, geodesic_farthest_point_sample_batched, geodesic_radius_edges)
+from .geodesic_support_graph import GeodesicSupportGraph
 
 __all__ = ['FCPrecomp', 'NormalizeArea', 'NormalizeAxes', 'SupportGraph', 'farthest_point_sample', 'load_precomp', 'radius_edges',
            'save_precomp', 'farthest_point_sample_batched', 'radius_edges_batched', 'SampleWeights', 'geodesic_distances',
-           'mesh_edge_graph', 'nearest_sample', 'sample_weights']
+           'mesh_edge_graph', 'nearest_sample', 'sample_weights', 'GeodesicSupportGraph', 'geodesic_farthest_point_sample',
+           'geodesic_farthest_point_sample_batched', 'geodesic_radius_edges']

@@ -765,6 +765,45 @@ int fc_geodesic_nearest(const int32_t* rowptr, const int32_t* nbr, const float* 
 int fc_face_areas(const float* pos, const int64_t* face, int32_t V, int32_t F, float* area, void* stream);
 int fc_segment_sum_f32(const float* x, const int64_t* ptr, int64_t N, int32_t K, float divisor, float* out, void* stream);
 
+/* ---- sampling and neighbourhoods by the edge-graph metric (csrc/fc_geodesic_fps.hip) -------------------------------------- *
+ * The graph, the lengths and the distance field d are those of the section above: every result is a function of least
+ * fixpoints, the same bits whatever the schedule.  One workgroup of 1024 threads per problem, no atomics.  A relaxation pulls
+ * only the vertices a neighbour's drop has flagged, runs at most n + 1 sweeps, and a mesh runs exactly n_samples rounds.
+ * fps                B meshes in one launch: mesh b owns the vertices pos_ptr[b] .. pos_ptr[b+1] - 1 ((B+1) int64 in DEVICE
+ *                    memory, checked by the CALLER; null: one mesh, B = 1, max_range = V).  n_samples, start, out_ptr: B
+ *                    int64 each in device memory (also for one mesh).  idx[out_ptr[b] + k], k < n_samples[b], LOCAL to the
+ *                    mesh: idx[.. + 0] = start[b]; sample k+1 is the vertex not yet taken with the largest d_k, the field of
+ *                    the first k+1 samples (+inf is the largest value: other components and faceless vertices come first;
+ *                    ties to the lowest vertex; no vertex twice, even where zero-length edges leave d = 0 on vertices not
+ *                    taken).  1 <= n_samples[b] <= n_b, 0 <= start[b] < n_b, out_ptr[b] + n_samples[b] <= total_out.  dist
+ *                    (V): every mesh's final field.  sweeps: null, or B int64, the relaxation sweeps summed over the rounds.
+ *                    Each round starts from the previous field.  Workspace: 3 V bytes when max_range exceeds the LDS capacity.
+ * ball count / fill  S queries: query q is the single-source problem from sample_idx[q] ((S) int64 vertex numbers, STRICTLY
+ *                    ASCENDING, checked by the caller), relaxed only while candidates stay < epsilon (which leaves every
+ *                    distance < epsilon as in the unbounded problem).  Its rows are [q, j] for the positions j with
+ *                    d_q[sample_idx[j]] < epsilon (strict; j = q included), j ascending; with more than K of them the K
+ *                    smallest by (distance, position).  pos_ptr / sample_ptr: both null, or the (B+1) int64 device tables of
+ *                    the vertex ranges and the sample-position ranges: a query searches its own mesh.  count[q] = rows of
+ *                    query q (int32) for q0 <= q < q0 + nq.  The caller forms offsets (S+1) int64 = exclusive prefix sums in
+ *                    device memory and n_edges = offsets[S]; fill solves the queries again and writes edges (n_edges,2) int64
+ *                    and, unless null, edge_dist (n_edges) float32: the bits of fc_geodesic_rows' row q.  Workspace: when
+ *                    max_range exceeds the LDS capacity, one slot per query of the launch (the query below), else 0.
+ * max_range as above: the largest range; the kernels clamp what they read from the tables.  V, E, S < 2^31.  FC_ERR_WORKSPACE
+ * when a workspace is missing or smaller.  No allocation or synchronisation inside. */
+int32_t fc_geodesic_fps_lds_vertices(void);
+size_t fc_geodesic_fps_workspace_bytes(int32_t V, int32_t max_range);
+int fc_geodesic_fps(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr, int32_t B,
+                    int32_t max_range, const int64_t* n_samples, const int64_t* start, const int64_t* out_ptr, int64_t total_out,
+                    int64_t* idx, float* dist, int64_t* sweeps, void* workspace, size_t workspace_bytes, void* stream);
+size_t fc_geodesic_ball_workspace_bytes(int32_t max_range, int32_t queries);
+int fc_geodesic_ball_count(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                           const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S, int32_t q0,
+                           int32_t nq, float epsilon, int32_t K, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+int fc_geodesic_ball_fill(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                          const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S, int32_t q0,
+                          int32_t nq, float epsilon, int32_t K, const int64_t* offsets, int64_t n_edges, int64_t* edges, float* edge_dist,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
