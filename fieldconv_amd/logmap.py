@@ -1,0 +1,169 @@
+"""Per-edge log map and parallel transport on the device (csrc/fc_logmap.hip): the xp / logMag / logAng of the reference's
+computeLogXPort, by the discrete exponential map of Schmidt, Grimm and Wyvill (2006) over the edge-graph metric of
+fieldconv_amd.geodesic.
+
+This is NOT the Vector Heat Method the reference's fcutils solves, and no parity with it is claimed: the layers are
+gauge-equivariant, so any consistent choice of frames and transport is a valid input.  What it is instead: restatable.  Per
+query sample s the bounded distance field d of geodesic_radius_edges (the same bits on every schedule) fixes a shortest-path
+tree by integer and bit decisions only -- edge (u,v) is tight when fl32(d[u] + length) has the bits of d[v]; the hop count h is
+the least fixpoint of h[s] = 0, h[v] = 1 + min h[u] over tight edges; pred[v] is the lowest-numbered tight u with
+h[u] = h[v] - 1 -- and the tree is unfolded into s's tangent plane by smooth float32 arithmetic:
+X[s] = 1, L[s] = 0, X[v] = rho X[u], L[v] = L[u] + conj(X[u]) c (tests/_logmap_ref.py restates all of it in numpy).
+
+Conventions are those of geodesic.py: pos (V,3) float32, face (3,F) int64, on a ROCm device or on the host; the arithmetic
+runs on the device either way and results go back to pos's device.  There is no CPU arithmetic path.  Bad arguments raise
+ValueError before anything is launched.  Nothing here is differentiable."""
+import math
+
+import torch
+
+from . import _lib
+from .geodesic import _check_index, _check_mesh, _device_of, _face_on, _prepare, _ptr, _stream
+from .pooling import check_ptr, ptr_on
+
+# Reached vertices of one query whose tree state stays in LDS (fc_logmap_ball_lds_vertices: 36 B each, beside the 6 B per
+# vertex of the mesh's relaxation state); a larger ball keeps it in a workspace slot, with the same result.
+BALL_LDS_VERTICES = 1024
+_WORKSPACE_BYTES = 1 << 28          # queries per launch where slots are needed: at most 256 MiB of them
+_TREE_ENTRIES = 1 << 24             # return_tree: at most this many (query, vertex) pairs
+
+
+def _frames(p, f, dev):
+    """device tensors in, device tensors out"""
+    V, F = int(p.shape[0]), int(f.shape[1])
+    lib = _lib.load()
+    corner = f.t().reshape(-1)                      # entry 3 f + c: ascending by (face, corner)
+    order = torch.sort(corner, stable=True)
+    fptr = torch.searchsorted(order.values.contiguous(), torch.arange(V + 1, device=dev)).to(torch.int32)
+    fidx = (order.indices // 3).to(torch.int32).contiguous()
+    out = torch.empty((3, V, 3), dtype=torch.float32, device=dev)
+    _lib.check(lib.fc_vertex_frames(_ptr(p), _ptr(f), _ptr(fptr), _ptr(fidx), V, F, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()),
+               'fc_vertex_frames')
+    return out[0], out[1], out[2]
+
+
+def vertex_frames(pos, face):
+    """(normal, e1, e2), each (V,3) float32: normal[v] is the normalised sum of cross(p1 - p0, p2 - p0) over the faces that
+    name v (ascending face order, corners as stored; (0,0,1) where the sum vanishes or v is in no face), e1 =
+    normalize(cross(ref, normal)) with ref = (0,0,1) where |normal.z| < 0.95 and (1,0,0) elsewhere, e2 = cross(normal, e1).
+    Every operation is a float32 operation rounded on its own.  On the unit sphere with normal = pos these are the frames of
+    fieldconv_amd.data.synthetic."""
+    what = 'vertex_frames'
+    _check_mesh(pos, face, what)
+    dev = _device_of(pos)
+    with torch.cuda.device(dev):
+        p = pos.detach().to(dev).contiguous()
+        f = _face_on(face, int(pos.shape[0]), dev, what)
+        return tuple(t.to(pos.device) for t in _frames(p, f, dev))
+
+
+def _check_bound(bound, what):
+    try:
+        ok = not isinstance(bound, bool) and math.isfinite(float(bound)) and float(bound) > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'{what}: bound must be a finite number > 0, got {bound!r}')
+    return float(bound)
+
+
+def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_ptr=None, ptr=None, return_reached=False, *,
+                      return_tree=False, ball_lds_vertices=None):
+    """(logMag (E,) float32, logAng (E,) float32, xp (E,) complex64): for row [a, b] of supp_edges ((E,2) int64 POSITIONS in
+    sample_idx, rows in any order; they come back in the caller's order) the polar coordinates of log_a(b) in a's frame, and
+    the unit complex number that turns coordinates in a's frame into coordinates in b's frame after transport from a to b: the
+    convention of the reference's computeLogXPort, which FCPrecomp consumes.  A row [a, a] gives 0, 0, 1.
+
+    Frames are vertex_frames(pos, face).  Per query a the field d from sample_idx[a] is relaxed while candidates stay below
+    fl32(bound) (the field of geodesic_radius_edges), the tree pred is read off its bits (module docstring) and unfolded: for a
+    child v of u, c is p_v - p_u without its normal[u] component, in (e1[u], e2[u]), rescaled to the edge's length; rho is e1[u]
+    carried by the minimal rotation normal[u] -> normal[v], in v's frame.  X[v] = rho X[u], L[v] = L[u] + conj(X[u]) c; the
+    row is |L[t]|, atan2(im L[t], re L[t]) (0 at the origin) and X[t] for t = sample_idx[b].
+    A target NOT reached below bound (further away, or in another component) is unfolded as a child of the source over a
+    virtual edge of length |p_t - p_s|: the tangent-plane projection.  return_reached: also (E,) bool, False on those rows.
+    With GeodesicSupportGraph(epsilon)'s edges and bound = epsilon every row is reached.
+
+    pos_ptr, ptr: both None, or the (B+1,) int64 range tables of a MeshBatch (batch.pos_ptr over pos, batch.ptr over
+    sample_idx): a query solves its own mesh only.  graph: mesh_edge_graph(pos, face), to build it once per mesh.
+    The two keyword-only arguments serve the tests, not a pipeline.  return_tree (small cases): also pred and hops, (S,V)
+    int32 each: per query and vertex of its mesh the predecessor (a vertex number) and the hop count, -1 where there is
+    none.  ball_lds_vertices (at most BALL_LDS_VERTICES, the default): balls up to
+    this size keep their tree state in LDS, larger ones in a workspace slot; the result does not depend on it.
+    One workgroup per query; no atomics, two runs give the same bits."""
+    what = 'log_map_transport'
+    _check_mesh(pos, face, what)
+    V = int(pos.shape[0])
+    _check_index(sample_idx, V, what, 'sample_idx')
+    S = int(sample_idx.numel())
+    if not torch.is_tensor(supp_edges) or supp_edges.dim() != 2 or supp_edges.shape[1] != 2 or supp_edges.dtype != torch.int64:
+        raise ValueError(f'{what}: supp_edges must be an (E,2) int64 tensor, got '
+                         f'{(tuple(supp_edges.shape), supp_edges.dtype) if torch.is_tensor(supp_edges) else type(supp_edges).__name__}')
+    R = int(supp_edges.shape[0])
+    if R and (int(supp_edges.min()) < 0 or int(supp_edges.max()) >= S):
+        raise ValueError(f'{what}: supp_edges must hold positions in sample_idx, in [0, {S})')
+    bound = _check_bound(bound, what)
+    cap = BALL_LDS_VERTICES if ball_lds_vertices is None else ball_lds_vertices
+    if isinstance(cap, bool) or int(cap) != cap or not 0 <= cap <= BALL_LDS_VERTICES:
+        raise ValueError(f'{what}: ball_lds_vertices must be an integer in [0, {BALL_LDS_VERTICES}], got {ball_lds_vertices!r}')
+    cap = int(cap)
+    if return_tree and S * V > _TREE_ENTRIES:
+        raise ValueError(f'{what}: return_tree is for small cases, at most {_TREE_ENTRIES} (query, vertex) pairs, got {S} x {V}')
+    if (pos_ptr is None) != (ptr is None):
+        raise ValueError(f'{what}: pos_ptr and ptr go together (the ranges of a MeshBatch): give both or neither')
+    B, max_range, host_p, host_s = 1, V, None, None
+    if pos_ptr is not None:
+        host_p, host_s = check_ptr(pos_ptr, V, what, 'pos_ptr'), check_ptr(ptr, S, what, 'ptr')
+        if len(host_p) != len(host_s):
+            raise ValueError(f'{what}: pos_ptr describes {len(host_p) - 1} meshes, ptr {len(host_s) - 1}')
+        B = len(host_p) - 1
+        if B < 1:
+            raise ValueError(f'{what}: pos_ptr describes no mesh')
+        max_range = max(b - a for a, b in zip(host_p, host_p[1:]))
+        at = sample_idx.device
+        mesh_of = torch.searchsorted(torch.tensor(host_p, dtype=torch.int64, device=at), sample_idx.contiguous(), right=True) - 1
+        counts = torch.tensor([b - a for a, b in zip(host_s, host_s[1:])], dtype=torch.int64, device=at)
+        if bool((mesh_of != torch.repeat_interleave(torch.arange(B, device=at), counts)).any()):
+            raise ValueError(f'{what}: sample_idx of a mesh must name vertices of that mesh (rows of the union inside its pos_ptr range)')
+    p, _, (gptr, nbr, length), dev = _prepare(pos, face, graph, what)
+    lib = _lib.load()
+    if lib.fc_logmap_ball_lds_vertices() != BALL_LDS_VERTICES:
+        raise _lib.FieldConvNativeError(f'{what}: the library keeps {lib.fc_logmap_ball_lds_vertices()} ball vertices in LDS, this module '
+                                        f'says {BALL_LDS_VERTICES}: they were built from different sources')
+    E_graph = int(nbr.numel())
+    per_call = S
+    slot = lib.fc_logmap_workspace_bytes(max_range, 1, cap)
+    if slot:
+        per_call = max(1, min(S, _WORKSPACE_BYTES // slot))
+    with torch.cuda.device(dev):
+        nrm, e1, e2 = _frames(p, _face_on(face, V, dev, what), dev)
+        src = sample_idx.detach().to(dev).contiguous()
+        rows = supp_edges.detach().to(dev)
+        order = torch.sort(rows[:, 0], stable=True)          # the rows grouped by query
+        row_ptr = torch.searchsorted(order.values.contiguous(), torch.arange(S + 1, device=dev))
+        target = rows[order.indices, 1].contiguous()
+        pp = sp = None
+        if pos_ptr is not None:
+            pp, sp = ptr_on(pos_ptr, host_p, dev), ptr_on(ptr, host_s, dev)
+        nbytes = lib.fc_logmap_workspace_bytes(max_range, per_call, cap)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        mag = torch.empty(R, dtype=torch.float32, device=dev)
+        ang = torch.empty(R, dtype=torch.float32, device=dev)
+        xp = torch.empty((R, 2), dtype=torch.float32, device=dev)
+        reached = torch.empty(R, dtype=torch.uint8, device=dev)
+        pred = hops = None
+        if return_tree:
+            pred = torch.full((S, V), -1, dtype=torch.int32, device=dev)
+            hops = torch.full((S, V), -1, dtype=torch.int32, device=dev)
+        for q0 in range(0, S, per_call):
+            _lib.check(lib.fc_logmap(_ptr(gptr), _ptr(nbr), _ptr(length), V, E_graph, _ptr(pp), _ptr(sp), B, max_range, _ptr(p), _ptr(nrm),
+                                     _ptr(e1), _ptr(e2), _ptr(src), S, q0, min(per_call, S - q0), bound, _ptr(row_ptr), _ptr(target), R,
+                                     _ptr(mag), _ptr(ang), _ptr(xp), _ptr(reached), _ptr(pred), _ptr(hops), cap, _ptr(ws), nbytes,
+                                     _stream()), 'fc_logmap')
+        back = torch.empty_like(order.indices)
+        back[order.indices] = torch.arange(R, device=dev)          # the caller's row r is the grouped row back[r]
+        out = (mag[back].to(pos.device), ang[back].to(pos.device), torch.view_as_complex(xp[back].contiguous()).to(pos.device))
+        if return_reached:
+            out += (reached[back].to(torch.bool).to(pos.device),)
+        if return_tree:
+            out += (pred.to(pos.device), hops.to(pos.device))
+    return out

@@ -7,8 +7,11 @@ from .support_graph import (SupportGraph, farthest_point_sample, farthest_point_
 from ..geodesic import geodesic_distances, mesh_edge_graph, nearest_sample, sample_weights
 from ..geodesic_sampling import (geodesic_farthest_point_sample, geodesic_farthest_point_sample_batched, geodesic_radius_edges)
 from .geodesic_support_graph import GeodesicSupportGraph
+from ..logmap import log_map_transport, vertex_frames
+from .compute_log_xport import ComputeLogXPort, computeLogXPort
 
 __all__ = ['FCPrecomp', 'NormalizeArea', 'NormalizeAxes', 'SupportGraph', 'farthest_point_sample', 'load_precomp', 'radius_edges',
            'save_precomp', 'farthest_point_sample_batched', 'radius_edges_batched', 'SampleWeights', 'geodesic_distances',
            'mesh_edge_graph', 'nearest_sample', 'sample_weights', 'GeodesicSupportGraph', 'geodesic_farthest_point_sample',
-           'geodesic_farthest_point_sample_batched', 'geodesic_radius_edges']
+           'geodesic_farthest_point_sample_batched', 'geodesic_radius_edges', 'ComputeLogXPort', 'computeLogXPort', 'log_map_transport',
+           'vertex_frames']

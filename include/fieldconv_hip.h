@@ -804,6 +804,45 @@ int fc_geodesic_ball_fill(const int32_t* rowptr, const int32_t* nbr, const float
                           int32_t nq, float epsilon, int32_t K, const int64_t* offsets, int64_t n_edges, int64_t* edges, float* edge_dist,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- log map and parallel transport by the discrete exponential map (csrc/fc_logmap.hip) ----------------------------------- *
+ * Schmidt, Grimm, Wyvill 2006 over the edge-graph metric of the sections above; not the Vector Heat Method of the reference's
+ * fcutils, and no parity with it.  The graph, the lengths and the bounded field d are those of the ball search.
+ * frames             face_ptr (V+1) / face_idx (3F) int32: a CSR over the vertices of the faces that name them, one entry per
+ *                    corner, ascending by (face, corner); built by the caller.  normal[v] = the sum of cross(p1 - p0, p2 - p0)
+ *                    over that list (corners as stored), divided by its norm; (0,0,1) where the norm is 0.  ref = (0,0,1) where
+ *                    |normal.z| < 0.95, else (1,0,0); e1 = normalize(cross(ref, normal)), e2 = cross(normal, e1).  Each (V,3)
+ *                    float32, every operation rounded on its own: a numpy float32 restatement gives the same bits.
+ * logmap             S queries as in the ball search (pos_ptr / sample_ptr / B / max_range / q0 / nq likewise; sample_idx need not
+ *                    ascend).  Query q owns the rows row_ptr[q] .. row_ptr[q+1] - 1 ((S+1) int64 in device memory, clamped to
+ *                    [0,n_rows]); row r names its target sample row_target[r], a position in sample_idx.  Per query: d bounded by
+ *                    `bound` (candidates >= bound discarded); edge (u,v) is tight when both ends are reached and
+ *                    fl32(d[u] + length) has the bits of d[v]; h = the least fixpoint of h[source] = 0, h[v] = 1 + min h[u] over
+ *                    tight (u,v); pred[v] = the lowest-numbered tight u with h[u] = h[v] - 1.  Along pred, in float32:
+ *                    X[source] = 1, L[source] = 0, X[v] = rho X[u], L[v] = L[u] + conj(X[u]) c, where c is p_v - p_u without its
+ *                    normal[u] component, in u's frame, rescaled to the edge's length (0 where nothing is left), and rho is e1[u]
+ *                    carried by the minimal rotation normal[u] -> normal[v], in v's frame, normalised (1 + n_u.n_v <= 1e-6: e1[u]
+ *                    projected onto v's plane; 1 where that vanishes).  Row r: log_mag = |L[t]|, log_ang = atan2(im, re) (0 at
+ *                    the origin), xp (n_rows,2) = X[t] (re, im), reached = 1.  A target not reached below the bound is unfolded
+ *                    as a child of the source over a virtual edge of length |p_t - p_source|, with reached = 0.
+ *                    debug_pred / debug_hops: both null, or (S,V) int32 set to -1 by the caller: the query's row gets pred (a
+ *                    vertex number) and h of the vertices of its range, -1 where there is none.
+ *                    ball_lds (at most fc_logmap_ball_lds_vertices): a ball of at most this many reached vertices keeps its tree
+ *                    state in LDS, a larger one in the workgroup's workspace slot: the same bits either way.
+ *                    A query whose source lies outside its range, or whose range exceeds max_range, gets NaN rows with
+ *                    reached = 0.
+ * One workgroup of 1024 threads per query writes that query's rows and slot only; no atomics, the same bits on every run;
+ * every loop is bounded by the size of the range.  Workspace: the query below (0 when max_range fits both LDS capacities);
+ * FC_ERR_WORKSPACE when missing or smaller.  No allocation or synchronisation inside. */
+int32_t fc_logmap_ball_lds_vertices(void);
+int fc_vertex_frames(const float* pos, const int64_t* face, const int32_t* face_ptr, const int32_t* face_idx, int32_t V, int32_t F,
+                     float* normal, float* e1, float* e2, void* stream);
+size_t fc_logmap_workspace_bytes(int32_t max_range, int32_t queries, int32_t ball_lds);
+int fc_logmap(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+              const int64_t* sample_ptr, int32_t B, int32_t max_range, const float* pos, const float* normal, const float* e1, const float* e2,
+              const int64_t* sample_idx, int32_t S, int32_t q0, int32_t nq, float bound, const int64_t* row_ptr, const int64_t* row_target,
+              int64_t n_rows, float* log_mag, float* log_ang, float* xp, uint8_t* reached, int32_t* debug_pred, int32_t* debug_hops,
+              int32_t ball_lds, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
