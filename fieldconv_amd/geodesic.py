@@ -1,8 +1,9 @@
 """Mesh geodesics on the device (csrc/fc_geodesic.hip): shortest paths over the mesh's edge graph, from one source or many.
 
 This is the EDGE-GRAPH metric, not the heat method the reference's fcutils solves: paths run along triangle sides, so a
-distance overestimates the true geodesic by up to a few percent on irregular meshes, and nearest-sample cells agree with
-the true ones except near cell boundaries.  What it buys: the result is deterministic and restatable bit for bit (a heap
+distance overestimates the true geodesic -- by 6 to 7 % on average and up to 23 % on a sphere, however fine the mesh; with the
+unfolded diagonals of mesh_edge_graph(..., diagonals=True) by about 1 % on average and up to 5 % -- and nearest-sample cells
+agree with the true ones except near cell boundaries.  What it buys: the result is deterministic and restatable bit for bit (a heap
 Dijkstra with float32 additions gives the same numbers, tests/_geodesic_ref.py), as FPS and the radius search are.
 
 pos (V,3) float32, face (3,F) int64 (the PyG layout), on a ROCm device or on the host: the arithmetic runs on the device
@@ -78,7 +79,7 @@ def _graph_on(graph, V, dev, what):
     return tuple(t.detach().to(dev).contiguous() for t in graph)
 
 
-def _edge_graph(p, f, dev):
+def _edge_graph(p, f, dev, diagonals=False):
     """device tensors in, device tensors out"""
     V = int(p.shape[0])
     a = torch.cat((f[0], f[1], f[2], f[1], f[2], f[0]))
@@ -92,12 +93,59 @@ def _edge_graph(p, f, dev):
     E = int(nbr.numel())
     length = torch.empty(E, dtype=torch.float32, device=dev)
     _lib.check(_lib.load().fc_mesh_edge_lengths(_ptr(p), _ptr(src), _ptr(nbr), V, E, _ptr(length), _stream()), 'fc_mesh_edge_lengths')
+    if diagonals:
+        return _with_diagonals(p, f, dev, src, nbr, length)
     return ptr, nbr, length
 
 
-def _prepare(pos, face, graph, what):
+def _with_diagonals(p, f, dev, src, nbr, length):
+    """the sides' CSR slots (src, nbr int32, length) -> (ptr, nbr, length) of the sides and the unfolded diagonals
+    (csrc/fc_mesh_graph.hip); sorting and compaction are torch, the geometry and the smallest-length rule are the kernels'"""
+    V, F = int(p.shape[0]), int(f.shape[1])
+    lib = _lib.load()
+    # half-edge 3 f + k: corner k -> corner k + 1, opposite corner k + 2; a stable sort keeps equal keys in ascending face order
+    a, b, o = f.t().reshape(-1), f[[1, 2, 0]].t().reshape(-1), f[[2, 0, 1]].t().reshape(-1)
+    key = torch.minimum(a, b) * V + torch.maximum(a, b)
+    key = torch.where((a == b) | (b == o) | (o == a), torch.full_like(key, V * V), key)          # (a degenerate face counts for no side)
+    order = torch.sort(key, stable=True)
+    N = 3 * F
+    lo = torch.empty(N, dtype=torch.int32, device=dev)
+    hi = torch.empty(N, dtype=torch.int32, device=dev)
+    dlen = torch.empty(N, dtype=torch.float32, device=dev)
+    _lib.check(lib.fc_mesh_diagonals(_ptr(p), _ptr(f), V, F, _ptr(order.values.contiguous()), _ptr(order.indices.contiguous()), N, _ptr(lo),
+                                     _ptr(hi), _ptr(dlen), _stream()), 'fc_mesh_diagonals')
+    found = lo >= 0
+    lo, hi, dlen = lo[found].to(torch.int64), hi[found].to(torch.int64), dlen[found]
+    keys = torch.cat((src.to(torch.int64) * V + nbr.to(torch.int64), lo * V + hi, hi * V + lo))
+    order = torch.sort(keys, stable=True)
+    keys, lens = order.values.contiguous(), torch.cat((length, dlen, dlen))[order.indices].contiguous()
+    N = int(keys.numel())
+    head = torch.empty(N, dtype=torch.uint8, device=dev)
+    msrc = torch.empty(N, dtype=torch.int32, device=dev)
+    mnbr = torch.empty(N, dtype=torch.int32, device=dev)
+    mlen = torch.empty(N, dtype=torch.float32, device=dev)
+    _lib.check(lib.fc_mesh_graph_merge(_ptr(keys), _ptr(lens), N, V, _ptr(head), _ptr(msrc), _ptr(mnbr), _ptr(mlen), _stream()),
+               'fc_mesh_graph_merge')
+    head = head.to(torch.bool)
+    msrc = msrc[head].to(torch.int64).contiguous()
+    ptr = torch.searchsorted(msrc, torch.arange(V + 1, device=dev)).to(torch.int32)
+    return ptr, mnbr[head].contiguous(), mlen[head].contiguous()
+
+
+def _check_diagonals(graph, diagonals, what):
+    if not isinstance(diagonals, bool):
+        raise ValueError(f'{what}: diagonals must be True or False, got {diagonals!r}')
+    if diagonals and graph is not None:
+        raise ValueError(f'{what}: graph= already decides which edges there are: build it with mesh_edge_graph(pos, face, diagonals=True) '
+                         'and leave diagonals at False')
+
+
+def _prepare(pos, face, graph, what, diagonals=False):
     """-> (pos, face or None, graph) on the device, and the device"""
     _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
+    if diagonals and 9 * face.shape[1] > 2 ** 31 - 1:
+        raise ValueError(f'{what}: with diagonals a mesh has up to 9 directed edges per face, and edges are 32-bit indices in the kernels')
     dev = _device_of(pos)
     V = int(pos.shape[0])
     with torch.cuda.device(dev):
@@ -105,25 +153,46 @@ def _prepare(pos, face, graph, what):
         if graph is not None:
             return p, None, _graph_on(graph, V, dev, what), dev
         f = _face_on(face, V, dev, what)
-        return p, f, _edge_graph(p, f, dev), dev
+        return p, f, _edge_graph(p, f, dev, diagonals), dev
 
 
-def mesh_edge_graph(pos, face):
+def mesh_edge_graph(pos, face, diagonals=False):
     """(ptr (V+1,) int32, nbr (E,) int32, length (E,) float32): the undirected triangle sides, duplicates removed, as a CSR
     over the vertices with neighbours ascending (every side appears in both rows; a vertex in no face has an empty row), and
     length = sqrt((dx*dx + dy*dy) + dz*dz) in float32, every operation rounded on its own.  Pass it as `graph=` to the
-    functions below to build it once per mesh."""
-    p, _, graph, _ = _prepare(pos, face, None, 'mesh_edge_graph')
+    functions below to build it once per mesh.
+
+    diagonals=True adds the UNFOLDED DIAGONALS (csrc/fc_mesh_graph.hip, restated in tests/_diagonal_graph_ref.py).  A path along
+    triangle sides can only head in six directions, which keeps the side graph's distances 6 to 7 % above the true geodesic on
+    average, up to 23 %, however fine the mesh; a diagonal joins the two vertices opposite an interior side across the unfolded
+    pair of triangles, which about doubles the directions (1 to 1.5 % on average, up to 5 %, on the same meshes) and the
+    degrees.  The result is a plain graph of the same layout, valid as `graph=` everywhere.
+    Candidate side: {u, v}, u < v, contained in exactly two faces, counting only faces with three distinct vertices; c and d
+    are the opposite vertices, c from the lower-numbered face, and must differ.  A boundary side (one face) and a non-manifold
+    side (three or more) give nothing.  Unfolding, in float32, every operation rounded on its own:
+        e = p_v - p_u, L2 = (ex*ex + ey*ey) + ez*ez (nothing when L2 == 0), L = sqrt(L2);
+        for w in (c, d): r = p_w - p_u, x_w = ((rx*ex + ry*ey) + rz*ez) / L, y_w = sqrt(max(((rx*rx + ry*ry) + rz*rz) - x_w*x_w, 0));
+        s = y_c + y_d (nothing when s <= 0); t = x_c + (x_d - x_c) * (y_c / s).
+    The diagonal {c, d} exists when 0 < t < L, both strict: the straight segment from c to d crosses the shared side in the
+    unfolded plane.  Its length is sqrt((x_c - x_d)*(x_c - x_d) + s*s).
+    Merge: the union of sides and diagonals over undirected pairs; a pair that arises more than once (from two interior sides, or
+    a diagonal that is also a side) keeps the smallest float32 length.  Every pair is computed once, in the orientation above,
+    so both CSR rows hold the same bits.  Diagonals come from faces, so in the union of a MeshBatch none crosses meshes."""
+    p, _, graph, _ = _prepare(pos, face, None, 'mesh_edge_graph', diagonals)
     return tuple(t.to(pos.device) for t in graph)
 
 
-def geodesic_distances(pos, face, sources, graph=None, rows_per_call=None, return_sweeps=False):
+def geodesic_distances(pos, face, sources, graph=None, rows_per_call=None, return_sweeps=False, diagonals=False):
     """(S,V) float32: row k holds the edge-graph distance from vertex sources[k] to every vertex, +inf where there is no
     path.  d is the least fixpoint of d[source] = 0, d[v] = min_u fl32(d[u] + length(u,v)): the bits of a heap Dijkstra
     with float32 additions.  One workgroup per row, launched rows_per_call rows at a time (default: 256 MiB of rows), so
-    for host tensors the device never holds more than one chunk.  return_sweeps: also the (S,) int32 sweep counts."""
+    for host tensors the device never holds more than one chunk.  return_sweeps: also the (S,) int32 sweep counts.
+    diagonals (here and in every function below that builds the graph itself when graph is None): over
+    mesh_edge_graph(pos, face, diagonals=True), the sides and the unfolded diagonals; together with an explicit graph= it raises
+    ValueError, because the graph already decides."""
     what = 'geodesic_distances'
     _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
     V = int(pos.shape[0])
     _check_index(sources, V, what, 'sources')
     S = int(sources.numel())
@@ -132,7 +201,7 @@ def geodesic_distances(pos, face, sources, graph=None, rows_per_call=None, retur
     if isinstance(rows_per_call, bool) or int(rows_per_call) != rows_per_call or rows_per_call < 1:
         raise ValueError(f'{what}: rows_per_call must be an integer >= 1, got {rows_per_call!r}')
     rows_per_call = min(int(rows_per_call), S)
-    p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what)
+    p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     E = int(nbr.numel())
     out = torch.empty((S, V), dtype=torch.float32, device=pos.device)
@@ -149,7 +218,7 @@ def geodesic_distances(pos, face, sources, graph=None, rows_per_call=None, retur
     return (out, sweeps[:, 0].to(pos.device)) if return_sweeps else out
 
 
-def nearest_sample(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=None, return_sweeps=False):
+def nearest_sample(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=None, return_sweeps=False, diagonals=False):
     """(label (V,) int64, dist (V,) float32): for every vertex the edge-graph distance to the nearest of the vertices
     sample_idx (S,) int64, and which one: label is a POSITION in sample_idx.  Labels are taken after the distances have
     converged, over the tight edges fl32(d[u] + length) == d[v]: label[v] is the smallest position whose sample reaches v
@@ -161,6 +230,7 @@ def nearest_sample(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=N
     return_sweeps: also the (B,2) int32 sweep counts (distance loop, label loop) per mesh."""
     what = 'nearest_sample'
     _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
     V = int(pos.shape[0])
     _check_index(sample_idx, V, what, 'sample_idx')
     S = int(sample_idx.numel())
@@ -175,7 +245,7 @@ def nearest_sample(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=N
         if any(b == a for a, b in zip(host_s, host_s[1:])):
             raise ValueError(f'{what}: a mesh of the batch has no samples')
         max_range = max(b - a for a, b in zip(host_p, host_p[1:]))
-    p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what)
+    p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     E = int(nbr.numel())
     with torch.cuda.device(dev):
@@ -198,13 +268,13 @@ def nearest_sample(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=N
     return out + (sweeps.to(pos.device),) if return_sweeps else out
 
 
-def samples_to_nearest(pos, face, samples):
+def samples_to_nearest(pos, face, samples, diagonals=False):
     """(V,) int64: for every vertex the position in `samples` of its nearest sample (fcutils' samplesToNearest and its
     argument order; by the edge-graph metric, ties to the lower position, -1 where no sample is reachable)."""
-    return nearest_sample(pos, face, samples)[0]
+    return nearest_sample(pos, face, samples, diagonals=diagonals)[0]
 
 
-def compose_map(labels_tem2tar, labels_tem2sour, pos, face):
+def compose_map(labels_tem2tar, labels_tem2sour, pos, face, diagonals=False):
     """(V,) int64 labels of the source mesh's vertices on the target (fcutils' composeMap and its argument order): template
     vertex l corresponds to vertex labels_tem2sour[l] - 1 of the source mesh (pos, face; 1-BASED, as in the label files)
     and to labels_tem2tar[l] on the target, so source vertex labels_tem2sour[l] - 1 gets labels_tem2tar[l] (the last l wins
@@ -222,7 +292,7 @@ def compose_map(labels_tem2tar, labels_tem2sour, pos, face):
     last = torch.full((V,), -1, dtype=torch.int64, device=pos.device)
     last.scatter_reduce_(0, hit_by, torch.arange(hit_by.numel(), device=pos.device), 'amax')
     hit = torch.nonzero(last >= 0)[:, 0]            # the vertices that were hit, ascending: the sources
-    label, _ = nearest_sample(pos, face, hit)
+    label, _ = nearest_sample(pos, face, hit, diagonals=diagonals)
     via = hit[label.clamp(min=0)]                   # (a vertex that was hit is its own nearest: distance 0, lowest position)
     return torch.where(label >= 0, tar[last[via]], torch.full_like(label, -1))
 
@@ -258,13 +328,13 @@ def vertex_masses(pos, face):
         return _segment_sum(_face_areas(p, f, dev).repeat(3), f.reshape(-1), int(p.shape[0]), 3.0, dev).to(pos.device)
 
 
-def sample_weights(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=None):
+def sample_weights(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=None, diagonals=False):
     """(S,1) float32, the reference's data.w (fcutils.weights): the lumped vertex masses (vertex_masses) summed onto each
     vertex's nearest sample (nearest_sample; with the two ptr tables per mesh of a MeshBatch).  The sum of a sample runs in
     float32 over its vertices in ascending order: no float atomics, two runs give the same bits.  A vertex no sample reaches
     (label -1) contributes to nothing."""
     what = 'sample_weights'
-    label, _ = nearest_sample(pos, face, sample_idx, pos_ptr, sample_ptr, graph)
+    label, _ = nearest_sample(pos, face, sample_idx, pos_ptr, sample_ptr, graph, diagonals=diagonals)
     dev = _device_of(pos)
     with torch.cuda.device(dev):
         mass = vertex_masses(pos, face).to(dev)
@@ -282,13 +352,14 @@ def surface_area(pos, face):
         return float(_face_areas(p, _face_on(face, int(pos.shape[0]), dev, what), dev).to(torch.float64).sum())
 
 
-def geodesic_error(pos, face, pred, target, normalize=True, graph=None, rows_per_call=None):
+def geodesic_error(pos, face, pred, target, normalize=True, graph=None, rows_per_call=None, diagonals=False):
     """(M,) float32: the edge-graph distance on the template (pos, face) between the predicted vertex pred[m] and the true
     vertex target[m] (both (M,) int64; e.g. LinearCrossEntropy.predict(h)[0][:, 0] and the labels), divided by sqrt(area)
     when normalize (the usual correspondence-benchmark convention).  Distance rows are solved for the DISTINCT targets only,
     rows_per_call at a time (geodesic_distances): the V x V matrix is never built."""
     what = 'geodesic_error'
     _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
     V = int(pos.shape[0])
     _check_index(target, V, what, 'target')
     _check_index(pred, V, what, 'pred')
@@ -299,7 +370,7 @@ def geodesic_error(pos, face, pred, target, normalize=True, graph=None, rows_per
     dev = _device_of(pos)
     with torch.cuda.device(dev):
         if graph is None:
-            graph = _prepare(pos, face, None, what)[2]
+            graph = _prepare(pos, face, None, what, diagonals)[2]
         uniq, inv = torch.unique(target.to(dev), return_inverse=True)
         pr = pred.to(dev)
         U = int(uniq.numel())

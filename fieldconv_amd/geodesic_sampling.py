@@ -12,7 +12,7 @@ ValueError before anything is launched.  Nothing here is differentiable."""
 import torch
 
 from . import _lib
-from .geodesic import _check_index, _check_mesh, _prepare, _ptr, _stream
+from .geodesic import _check_diagonals, _check_index, _check_mesh, _prepare, _ptr, _stream
 from .pooling import check_ptr, ptr_on
 
 # Vertices of one mesh solved in LDS (fc_geodesic_fps_lds_vertices: 7 B per vertex for sampling, 6 B for a ball); a larger
@@ -38,12 +38,12 @@ def _per_mesh(value, B, what, name):
     return vals
 
 
-def _fps(pos, face, pos_ptr, host_ptr, S, starts, graph, what):
+def _fps(pos, face, pos_ptr, host_ptr, S, starts, graph, what, diagonals=False):
     """S, starts: per-mesh Python ints, checked -> (idx (sum S,) int64 local, dist (V,), sweeps (B,) int64) on the device, and it"""
     V = int(pos.shape[0])
     B = len(S)
     max_range = V if host_ptr is None else max(b - a for a, b in zip(host_ptr, host_ptr[1:]))
-    p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what)
+    p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     out_ptr = [0]
     for s in S:
@@ -62,7 +62,7 @@ def _fps(pos, face, pos_ptr, host_ptr, S, starts, graph, what):
     return idx, dist, sweeps
 
 
-def geodesic_farthest_point_sample(pos, face, n_samples, start=0, graph=None, return_dist=False, return_sweeps=False):
+def geodesic_farthest_point_sample(pos, face, n_samples, start=0, graph=None, return_dist=False, return_sweeps=False, diagonals=False):
     """(n_samples,) int64 vertex numbers in selection order.  idx[0] = start; idx[k+1] is the vertex not yet taken with the
     largest d_k, where d_k is the multi-source distance field of idx[:k+1] (the bits of nearest_sample(pos, face, idx[:k+1])[1]).
     +inf is the largest value, so another component, or a vertex in no face, is sampled before any reached vertex; ties go to
@@ -70,13 +70,14 @@ def geodesic_farthest_point_sample(pos, face, n_samples, start=0, graph=None, re
     1 <= n_samples <= V, 0 <= start < V.  One launch: one workgroup runs all the rounds, each from the previous field.
     graph: mesh_edge_graph(pos, face), to build it once per mesh.  return_dist: also the final field d_{n_samples-1}, (V,)
     float32 (its maximum is the covering radius of the sample).  return_sweeps: also the relaxation sweeps summed over the
-    rounds, a () int64 tensor."""
+    rounds, a () int64 tensor.  diagonals: as in geodesic_distances (graph must then be None)."""
     what = 'geodesic_farthest_point_sample'
     _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
     V = int(pos.shape[0])
     S = _int_in(n_samples, 1, V, what, 'n_samples')
     st = _int_in(start, 0, V - 1, what, 'start')
-    idx, dist, sweeps = _fps(pos, face, None, None, [S], [st], graph, what)
+    idx, dist, sweeps = _fps(pos, face, None, None, [S], [st], graph, what, diagonals)
     out = (idx.to(pos.device),)
     if return_dist:
         out += (dist.to(pos.device),)
@@ -85,15 +86,18 @@ def geodesic_farthest_point_sample(pos, face, n_samples, start=0, graph=None, re
     return out if len(out) > 1 else out[0]
 
 
-def geodesic_farthest_point_sample_batched(pos, face, pos_ptr, n_samples, start=0, graph=None, return_dist=False, return_sweeps=False):
+def geodesic_farthest_point_sample_batched(pos, face, pos_ptr, n_samples, start=0, graph=None, return_dist=False, return_sweeps=False,
+                                           diagonals=False):
     """geodesic_farthest_point_sample for the B meshes of a union at once, one workgroup per mesh in one launch: mesh b is
     pos[pos_ptr[b]:pos_ptr[b+1]] (pos_ptr (B+1,) int64, host or device, checked on the host; face and graph are the union's),
     n_samples and start one integer for all meshes or one per mesh, 1 <= n_samples[b] <= n_b, 0 <= start[b] < n_b.  Returns the
     (sum n_samples,) int64 indices, mesh after mesh in selection order, each LOCAL to its mesh (add pos_ptr[b] for rows of pos),
     as farthest_point_sample_batched does: index for index what the single call gives for the mesh alone.
-    return_dist: also the (V,) final fields; return_sweeps: also the (B,) int64 sweep totals."""
+    return_dist: also the (V,) final fields; return_sweeps: also the (B,) int64 sweep totals.  diagonals: as in
+    geodesic_distances (graph must then be None); none crosses meshes."""
     what = 'geodesic_farthest_point_sample_batched'
     _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
     host = check_ptr(pos_ptr, int(pos.shape[0]), what, 'pos_ptr')
     B = len(host) - 1
     if B < 1:
@@ -105,7 +109,7 @@ def geodesic_farthest_point_sample_batched(pos, face, pos_ptr, n_samples, start=
             raise ValueError(f'{what}: mesh {b} holds no vertices')
         S[b] = _int_in(S[b], 1, n_b, what, 'n_samples', f' of mesh {b}')
         st[b] = _int_in(st[b], 0, n_b - 1, what, 'start', f' of mesh {b}')
-    idx, dist, sweeps = _fps(pos, face, pos_ptr, host, S, st, graph, what)
+    idx, dist, sweeps = _fps(pos, face, pos_ptr, host, S, st, graph, what, diagonals)
     out = (idx.to(pos.device),)
     if return_dist:
         out += (dist.to(pos.device),)
@@ -115,7 +119,7 @@ def geodesic_farthest_point_sample_batched(pos, face, pos_ptr, n_samples, start=
 
 
 def geodesic_radius_edges(pos, face, sample_idx, epsilon, max_num_neighbors=512, pos_ptr=None, sample_ptr=None, graph=None,
-                          return_dist=False):
+                          return_dist=False, diagonals=False):
     """(E,2) int64 rows [q, j], POSITIONS in sample_idx: one row for every pair with d_q[sample_idx[j]] < fl32(epsilon), where
     d_q is the single-source distance field of vertex sample_idx[q] (row q of geodesic_distances(pos, face, sample_idx)).
     The comparison is strict and q is its own neighbour.  Rows are grouped by q ascending, j ascending inside a group: the
@@ -127,10 +131,11 @@ def geodesic_radius_edges(pos, face, sample_idx, epsilon, max_num_neighbors=512,
     its own mesh only, and a batch of small meshes stays in LDS although their union would not.
     One workgroup per query relaxes only while candidates stay below epsilon: a prefix of a shortest path is never longer than
     the path, so every distance below epsilon is the unbounded one.  The queries are solved twice (count, then fill) around the
-    one synchronisation that sizes the output."""
+    one synchronisation that sizes the output.  diagonals: as in geodesic_distances (graph must then be None)."""
     from .transforms.support_graph import _check_epsilon, _check_k
     what = 'geodesic_radius_edges'
     _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
     V = int(pos.shape[0])
     _check_index(sample_idx, V, what, 'sample_idx')
     S = int(sample_idx.numel())
@@ -154,7 +159,7 @@ def geodesic_radius_edges(pos, face, sample_idx, epsilon, max_num_neighbors=512,
         counts = torch.tensor([b - a for a, b in zip(host_s, host_s[1:])], dtype=torch.int64, device=at)
         if bool((mesh_of != torch.repeat_interleave(torch.arange(B, device=at), counts)).any()):
             raise ValueError(f'{what}: sample_idx of a mesh must name vertices of that mesh (rows of the union inside its pos_ptr range)')
-    p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what)
+    p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     E_graph = int(nbr.numel())
     per_call = S

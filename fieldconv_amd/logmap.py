@@ -18,7 +18,7 @@ import math
 import torch
 
 from . import _lib
-from .geodesic import _check_index, _check_mesh, _device_of, _face_on, _prepare, _ptr, _stream
+from .geodesic import _check_diagonals, _check_index, _check_mesh, _device_of, _face_on, _prepare, _ptr, _stream
 from .pooling import check_ptr, ptr_on
 
 # Reached vertices of one query whose tree state stays in LDS (fc_logmap_ball_lds_vertices: 36 B each, beside the 6 B per
@@ -68,7 +68,7 @@ def _check_bound(bound, what):
 
 
 def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_ptr=None, ptr=None, return_reached=False, *,
-                      return_tree=False, ball_lds_vertices=None):
+                      return_tree=False, ball_lds_vertices=None, diagonals=False):
     """(logMag (E,) float32, logAng (E,) float32, xp (E,) complex64): for row [a, b] of supp_edges ((E,2) int64 POSITIONS in
     sample_idx, rows in any order; they come back in the caller's order) the polar coordinates of log_a(b) in a's frame, and
     the unit complex number that turns coordinates in a's frame into coordinates in b's frame after transport from a to b: the
@@ -85,6 +85,10 @@ def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_
 
     pos_ptr, ptr: both None, or the (B+1,) int64 range tables of a MeshBatch (batch.pos_ptr over pos, batch.ptr over
     sample_idx): a query solves its own mesh only.  graph: mesh_edge_graph(pos, face), to build it once per mesh.
+    diagonals: over mesh_edge_graph(pos, face, diagonals=True) (graph must then be None; a graph built with diagonals may be
+    passed as graph= as well).  The unfolding step takes any edge (u, v, length): over a diagonal the chord p_v - p_u of the two
+    triangles is projected into u's tangent plane and rescaled to the diagonal's unfolded length -- the approximation made for a
+    side, applied to a two-triangle chord.
     The two keyword-only arguments serve the tests, not a pipeline.  return_tree (small cases): also pred and hops, (S,V)
     int32 each: per query and vertex of its mesh the predecessor (a vertex number) and the hop count, -1 where there is
     none.  ball_lds_vertices (at most BALL_LDS_VERTICES, the default): balls up to
@@ -92,6 +96,7 @@ def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_
     One workgroup per query; no atomics, two runs give the same bits."""
     what = 'log_map_transport'
     _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
     V = int(pos.shape[0])
     _check_index(sample_idx, V, what, 'sample_idx')
     S = int(sample_idx.numel())
@@ -124,7 +129,7 @@ def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_
         counts = torch.tensor([b - a for a, b in zip(host_s, host_s[1:])], dtype=torch.int64, device=at)
         if bool((mesh_of != torch.repeat_interleave(torch.arange(B, device=at), counts)).any()):
             raise ValueError(f'{what}: sample_idx of a mesh must name vertices of that mesh (rows of the union inside its pos_ptr range)')
-    p, _, (gptr, nbr, length), dev = _prepare(pos, face, graph, what)
+    p, _, (gptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     if lib.fc_logmap_ball_lds_vertices() != BALL_LDS_VERTICES:
         raise _lib.FieldConvNativeError(f'{what}: the library keeps {lib.fc_logmap_ball_lds_vertices()} ball vertices in LDS, this module '

@@ -13,10 +13,15 @@ class ComputeLogXPort(object):
     GeodesicSupportGraph(epsilon) every target is inside its source's tree; after the Euclidean SupportGraph a target further
     than bound along the surface falls back to the tangent-plane projection of the chord (log_map_transport).
     A fieldconv_amd.data.MeshBatch (pos_ptr and ptr present) is handled in one launch per kernel, every query inside its own
-    mesh: mesh for mesh what the single-mesh call gives."""
+    mesh: mesh for mesh what the single-mesh call gives.
+    diagonals=True grows the trees, and finds data.w's nearest samples, over mesh_edge_graph(pos, face, diagonals=True); after
+    GeodesicSupportGraph(epsilon, diagonals=True) every target is again inside its source's tree."""
 
-    def __init__(self, bound):
+    def __init__(self, bound, diagonals=False):
         self.bound = _check_bound(bound, 'ComputeLogXPort')
+        if not isinstance(diagonals, bool):
+            raise ValueError(f'ComputeLogXPort: diagonals must be True or False, got {diagonals!r}')
+        self.diagonals = diagonals
 
     def __call__(self, data):
         for name in ('pos', 'face', 'sample_idx', 'supp_edges'):
@@ -28,13 +33,13 @@ class ComputeLogXPort(object):
             raise ValueError('ComputeLogXPort: a batch needs ptr, the ranges of the sampled vertices')
         if pos_ptr is None:
             ptr = None
-        graph = mesh_edge_graph(pos, data.face)
+        graph = mesh_edge_graph(pos, data.face, self.diagonals)
         data.logMag, data.logAng, data.xp = log_map_transport(pos, data.face, data.sample_idx.to(pos.device), data.supp_edges.to(pos.device),
                                                               self.bound, graph=graph, pos_ptr=pos_ptr, ptr=ptr)
-        return SampleWeights()(data)
+        return SampleWeights(graph=graph)(data)
 
     def __repr__(self):
-        return '{}(bound={})'.format(self.__class__.__name__, self.bound)
+        return '{}(bound={}{})'.format(self.__class__.__name__, self.bound, ', diagonals=True' if self.diagonals else '')
 
 
 computeLogXPort = ComputeLogXPort

@@ -843,6 +843,34 @@ int fc_logmap(const int32_t* rowptr, const int32_t* nbr, const float* length, in
               int64_t n_rows, float* log_mag, float* log_ang, float* xp, uint8_t* reached, int32_t* debug_pred, int32_t* debug_hops,
               int32_t ball_lds, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the edge graph enriched by unfolded diagonals (csrc/fc_mesh_graph.hip) -------------------------------------------------- *
+ * Beside the triangle sides, the graph gets one edge across every interior side whose two faces unfold into a quadrilateral that
+ * the straight segment between the opposite vertices stays inside.  Float32 throughout, every operation rounded on its own.
+ * diagonals          face (3,F) int64; half-edge h = 3 f + k runs from corner k of face f to corner k + 1 and has corner k + 2
+ *                    opposite.  key (N) int64, N <= 3 F: one entry per half-edge, equal exactly for the half-edges of one
+ *                    undirected side, SORTED ascending with ties by ascending face; half (N) int64: the half-edge of each entry.
+ *                    Half-edges of faces that name a vertex twice must not share a key with any other (the caller gives them a
+ *                    key above every side's, or leaves them out).  Slot i is a candidate when it is the first of a run of exactly
+ *                    two equal keys, both half-edges lie on the same side {u, v}, u < v, and the opposite vertices c (slot i) and
+ *                    d (slot i + 1) differ.  Then e = p_v - p_u, L2 = (ex ex + ey ey) + ez ez (nothing when L2 == 0),
+ *                    L = sqrt(L2); for w in (c, d): r = p_w - p_u, x_w = ((rx ex + ry ey) + rz ez) / L,
+ *                    y_w = sqrt(max(((rx rx + ry ry) + rz rz) - x_w x_w, 0)); s = y_c + y_d (nothing when s <= 0);
+ *                    t = x_c + (x_d - x_c) (y_c / s); the diagonal exists when 0 < t < L, both strict, and then
+ *                    lo[i] = min(c, d), hi[i] = max(c, d), length[i] = sqrt((x_c - x_d) (x_c - x_d) + s s).  Every other slot
+ *                    gets lo = hi = -1 and length NaN.  An index outside its range makes a slot no candidate and reads nothing.
+ * merge              key (N) int64 SORTED ascending: the directed entries u V + v of sides and diagonals, both directions of
+ *                    each; length (N) in the same order.  head[i] = 1 at the first entry of every run of equal keys inside
+ *                    [0, V V), and there src[i] = u, nbr[i] = v, out_length[i] = the run's lengths folded from its first entry by
+ *                    m = x < m ? x : m (the smallest; both directions of a pair hold the same lengths, so the same bits).  Every
+ *                    other slot gets head 0, src = nbr = -1, NaN.  The heads, in order, are the CSR's slots by row with neighbours
+ *                    ascending; the caller compacts them.
+ * One thread per slot, each slot written by its own thread only: no atomics, the same bits on every run.  V, N < 2^31.  No
+ * allocation or synchronisation inside. */
+int fc_mesh_diagonals(const float* pos, const int64_t* face, int32_t V, int32_t F, const int64_t* key, const int64_t* half, int32_t N,
+                      int32_t* lo, int32_t* hi, float* length, void* stream);
+int fc_mesh_graph_merge(const int64_t* key, const float* length, int32_t N, int32_t V, uint8_t* head, int32_t* src, int32_t* nbr,
+                        float* out_length, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
