@@ -23,7 +23,8 @@ SWITCHES = {
     'FC_SPLIT_FINISH': '1: partial sums and parameter-gradient chain as two launches',
     'FC_EDGE_PARTS_MAX': 'cap (log2) on the number of workgroups that share a tile on small meshes',
     'FC_ECHO_WPV': 'wavefronts per vertex in the ECHO descriptor kernels (1, 2 or 4)',
-    'FC_STAMP_KERNEL': 'data | filter | stream: which backward kernel writes in-kernel time stamps (tools/stamps.py)',
+    'FC_STAMP_KERNEL': 'data | filter | stream: which backward kernel writes in-kernel time stamps (tools/stamps.py); waits: the walk kernels sum '
+                       'the cycles of their explicit vector-memory waits instead (tools/wait_cost.py)',
     'FC_DEBUG': 'forward kernels: skip phases (WRONG RESULTS; refused by bench.py)',
     'FC_DEBUG_BWD': 'backward kernels: skip phases (bit 0 walk, bit 1 gxt product, bit 2 gW product, bit 3 H stores) (WRONG RESULTS; refused by bench.py)',
     'FC_LIN_DIRECT': '0: TangentLin on small meshes through the LDS-staged kernel instead of the direct one',

@@ -53,6 +53,7 @@ struct StreamArgs {
     int nt_dump;
     uint32_t* wst;           // [F][G][kStreamUnits][re_hi, re_lo, im_hi, im_lo][64 lanes][4 dwords]: written by the gather launch, read by the streaming one
     unsigned long long* stamps;   // development only (fc_debug_stamp_buffer, FC_STAMP_KERNEL=stream): s_memtime stamps of workgroup (0, 0)
+    unsigned long long* meter;    // development only (FC_STAMP_KERNEL=waits): the cost of the gather kernel's explicit vector-memory waits (WaitMeter)
     int dbg;                 // development only (FC_DEBUG_BWD): bit0 no walk, bit1 no gxt product, bit2 no gW product, bit3 no H stores,
                              // bit4 the stream kernel re-reads its first record (L2), bit5 H stored with the default cache policy, bit6 records last-produced first
 };
@@ -139,6 +140,8 @@ inline StreamArgs make_stream_args(const fc_dims* d, const StreamPlan& p) {
     a.dbg = dbg;
     static const bool stamp_me = [] { const char* e = dev_env("FC_STAMP_KERNEL"); return e && e[0] == 's'; }();
     a.stamps = stamp_me ? debug_stamp_buffer() : nullptr;
+    static const bool meter_me = [] { const char* e = dev_env("FC_STAMP_KERNEL"); return e && e[0] == 'w'; }();
+    a.meter = meter_me && debug_stamp_buffer() ? debug_stamp_buffer() + kMeterGather : nullptr;
     return a;
 }
 
@@ -226,6 +229,8 @@ __global__ __launch_bounds__(WPG * kWave, MINW) void fc_backward_gather_kernel(
     // lanes of a vertex's row: output channel o = lane; with two slices per frequency the lanes [0, O/2) and [O/2, O) store into the
     // records of the first and of the second half of the o-major k range
     const int OH = O / a.KS;
+    WaitMeter meter;
+    meter.open(a.meter);
     for (int item = first_tile_of_block(); item < nitems; item += grid) {
         int nbeg = 0, nend = 0, nro[R];
         slot_range(item + grid, nbeg, nend, nro);
@@ -248,7 +253,9 @@ __global__ __launch_bounds__(WPG * kWave, MINW) void fc_backward_gather_kernel(
             // ---------------------------------------------------------------- the walk (fc_backward_data_kernel's, one group)
             float2 ga = make_float2(0.f, 0.f), gb = ga;
             if (nslots > 0) {
+                meter.begin();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // first chunks have landed
+                meter.end(2);
                 const int d0 = __float_as_int(rec_ptr(0)[3]);
                 const int d1 = __float_as_int(rec_ptr(min(1, nslots - 1))[3]);
                 ga = gather_row(ggy, d0, 8u * O, 8u * ol);
@@ -283,8 +290,11 @@ __global__ __launch_bounds__(WPG * kWave, MINW) void fc_backward_gather_kernel(
                     while (s < run_end) {
                         const int m = s & (CR - 1);
                         if (m == 0 && s > 0) {       // entering a chunk: the one before it is consumed, its ring slot refilled
+                            // NO wait: the chunk entered was requested (NR - 1) CR slots ago, and slot s + 2 uses the row that slot s
+                            // requested -- vmcnt retires in issue order, so from the third slot behind a chunk's request on it has
+                            // landed (fc_forward_ring.hpp, ring_landed); the first NR chunks are waited for at the walk's start
+                            static_assert((NR - 1) * CR >= 3, "a chunk is entered at least three slots behind its request");
                             const int ch = s >> LOG_CR;
-                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                             if (ch - 1 + NR < nch) dma_chunk(beg, ch - 1 + NR);
                         }
                         const int stop = min(run_end, s - m + CR);
@@ -303,8 +313,14 @@ __global__ __launch_bounds__(WPG * kWave, MINW) void fc_backward_gather_kernel(
                     }
                 });
             }
-            {   // this walk is done: stream the first record chunks of the next one -- my source again, or my next tile's source
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            {   // this walk is done: stream the first record chunks of the next one -- my source again, or my next tile's source.  Every
+                // chunk of this walk has landed (above); its last record reads have returned; the two look-ahead rows still in flight
+                // are read by nobody, so no vector-memory wait
+                meter.begin();
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                meter.end(1);
+                meter.begin();
+                meter.end(7);
                 if constexpr (GI + 1 < NG) {
                     for (int ch = 0; ch < min(nch, NR); ++ch) dma_chunk(beg, ch);
                 } else {
@@ -375,6 +391,8 @@ __global__ __launch_bounds__(WPG * kWave, MINW) void fc_backward_gather_kernel(
 #pragma unroll
         for (int q = 0; q < R; ++q) ro[q] = nro[q];
     }
+
+    meter.close();
 
     // ---- a rider for the launch that follows: the filter fragments of the streaming kernel's gxt wavefronts, copied out of the packed
     // backward image in the order those wavefronts load them -- entry ((f*G + g)*kStreamUnits + ui)*4 + plane, 64 lanes x 16 bytes:

@@ -334,4 +334,50 @@ struct Stamper {
     }
 };
 
+// Cost of the walk kernels' explicit vector-memory waits (development library only; FC_STAMP_KERNEL=waits, tools/wait_cost.py): every
+// wavefront of the launch sums, per kind of wait, the shader cycles between begin() and end(kind) in scalar registers and adds them to
+// the stamp buffer when it leaves: p[kind] cycles, p[8 + kind] waits, p[16] the wavefronts' own cycles, p[17] wavefronts.  Kind 7 is
+// a begin() / end() pair around nothing, once per target: what the two clock reads themselves cost.
+struct WaitMeter {
+    static constexpr int kKinds = 8;
+    unsigned long long* p;      // wave-uniform: this kernel's 32 slots of the stamp buffer, or nullptr
+    unsigned long long t0, start, cyc[kKinds];
+    unsigned n[kKinds];
+    __device__ __forceinline__ void open(unsigned long long* q) {
+        p = nullptr;
+        if constexpr (kDevSwitches) {
+            p = q;
+            if (p) {
+                start = __builtin_amdgcn_s_memtime();
+#pragma unroll
+                for (int k = 0; k < kKinds; ++k) { cyc[k] = 0; n[k] = 0; }
+            }
+        }
+    }
+    __device__ __forceinline__ void begin() {
+        if constexpr (kDevSwitches)
+            if (p) t0 = __builtin_amdgcn_s_memtime();
+    }
+    __device__ __forceinline__ void end(const int kind) {
+        if constexpr (kDevSwitches)
+            if (p) {
+                cyc[kind] += __builtin_amdgcn_s_memtime() - t0;
+                ++n[kind];
+            }
+    }
+    __device__ __forceinline__ void close() {
+        if constexpr (kDevSwitches)
+            if (p && (threadIdx.x & 63) == 0) {
+#pragma unroll
+                for (int k = 0; k < kKinds; ++k) {
+                    atomicAdd(p + k, cyc[k]);
+                    atomicAdd(p + kKinds + k, (unsigned long long)n[k]);
+                }
+                atomicAdd(p + 16, __builtin_amdgcn_s_memtime() - start);
+                atomicAdd(p + 17, 1ull);
+            }
+    }
+};
+constexpr int kMeterForward = 0, kMeterGather = 32;      // the two kernels' slots in the stamp buffer
+
 }  // namespace fc

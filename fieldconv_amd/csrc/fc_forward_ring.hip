@@ -71,7 +71,9 @@ int forward_ring_impl(const float* x, const float* rec, const fc_csr* g, const f
     a.slab_bytes_w = (uint32_t)(2 * p.g.split * p.g.MP * p.g.KP * 2);
     static const int dbg = [] { const char* e = dev_env("FC_DEBUG"); return e ? atoi(e) : 0; }();
     a.dbg = dbg;
-    a.stamps = debug_stamp_buffer();
+    static const bool meter = [] { const char* e = dev_env("FC_STAMP_KERNEL"); return e && e[0] == 'w'; }();
+    a.stamps = meter ? nullptr : debug_stamp_buffer();
+    a.meter = meter && debug_stamp_buffer() ? debug_stamp_buffer() + kMeterForward : nullptr;
     const int nvt = a.ntiles << a.parts_log2;
     int grid = nvt < 2 * num_cus() ? nvt : 2 * num_cus();            // persistent: two workgroups per CU
     // the last, partly filled round: as half tiles when those still fit one round

@@ -53,6 +53,7 @@ struct RingArgs {
     int dbg;                // development only (FC_DEBUG): bit0 skip gather, bit1 skip MFMA
     FwdEpi epi;             // residual / modReLU applied to the output tile (when parts_log2 == 0; otherwise after the parts' sum)
     unsigned long long* stamps;   // development only (fc_debug_stamp_buffer): s_memtime stamps of workgroup 0, [8 waves][256]
+    unsigned long long* meter;    // development only (FC_STAMP_KERNEL=waits): the cost of the explicit vector-memory waits (WaitMeter)
 };
 
 // Contraction geometry of a ring slab for an eight-wavefront workgroup: wavefront w owns output tile w % NMT and the k
@@ -127,6 +128,8 @@ __global__ __launch_bounds__(kDuoThreads, 4) void fc_forward_ring_kernel(
     // priority for the younger half evens that out (MI355X_MICROARCH.md, "Two waves per SIMD", item 4).
     if (wave >= kDuoWaves / 2 && !(a.dbg & 4)) __builtin_amdgcn_s_setprio(1);
     Stamper stamp{(a.stamps && blockIdx.x == 0) ? a.stamps + wave * 256 : nullptr, 0};
+    WaitMeter meter;
+    meter.open(a.meter);
     const int cl = lane < I ? lane : 0;      // lanes >= I gather channel 0; lanes >= KI are never stored
     const int mt = wave % g.NMT, kp = wave / g.NMT;
     const bool mma_active = kp < g.NKP;
@@ -196,7 +199,9 @@ __global__ __launch_bounds__(kDuoThreads, 4) void fc_forward_ring_kernel(
         const int nch = (end[j] - beg[j] + CR - 1) >> LOG_CR;
         for (int ch = 0; ch < min(nch, nr); ++ch) dma_chunk(j, beg[j], ch);
     }
+    meter.begin();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // first chunks have landed
+    meter.end(4);
     float2 px[2][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) first_rows(j, end[j] - beg[j], px[j][0], px[j][1]);
@@ -309,6 +314,24 @@ __global__ __launch_bounds__(kDuoThreads, 4) void fc_forward_ring_kernel(
         // rows of the next even / odd slot (a slot requests the row of slot + 2 into its own registers: no rotation at odd run
         // ends).  The record ring's events -- a chunk is entered, the look-ahead is about to leave the chunk -- are handled
         // between SEGMENTS of the run, so that the slots themselves carry no checks.
+        //
+        // ring_landed -- why a record chunk is never waited for inside the walk.  vmcnt retires in issue order, and the compiler puts its
+        // own s_waitcnt vmcnt(N) in front of the first use of every row value.  Slot s requests the row of slot s + 2, so when slot
+        // s + 2 of a stream has used its row, everything this wavefront requested before slot s has landed -- record chunks (the
+        // LDS-DMA, which the compiler does not count: it only makes its N stricter) and the other stream's requests alike.  The slots
+        // of a stream are walked in order, without gaps, by this wavefront; so:
+        //   * chunk ch >= nr is requested at the entry of chunk ch - nr + 1, in front of that chunk's first slot, and first read when
+        //     chunk ch is entered, (nr - 1) CR >= 4 slots later, or by the look-ahead at position CR - 2 of chunk ch - 1 (nr == 2:
+        //     CR - 2 slots later): proven from three slots on, i.e. for CR >= 8 (kLookaheadProven); with four-record chunks the
+        //     look-ahead keeps a COUNTED wait;
+        //   * chunks 0 .. nr - 1 are requested when the previous tile's targets are done and waited for once, in front of first_rows;
+        //   * a short target, a run that ends right behind a chunk entry and the switch to the other stream change none of this: the
+        //     count is of this stream's slots since the request, wherever the runs end;
+        //   * at the end of a target every chunk it requested has therefore landed, and the next tile's first chunks are requested
+        //     without a wait: what is still in flight then are the two look-ahead rows of each stream, which nobody reads.
+        // The refill of a ring slot follows the last LDS reads of the chunk it held in program order; those reads have returned (their
+        // values fed the slot's arithmetic) before the request is even issued.
+        constexpr bool kLookaheadProven = CR - 2 >= 3;
         auto gather_run = [&](const int j, int s, const int run_end, f32x2 (&lo)[F], f32x2 (&hi)[F], float2& xe, float2& xo) {
             const float* const ring = ring_of(j);
             const int nslots = end[j] - beg[j];
@@ -343,16 +366,23 @@ __global__ __launch_bounds__(kDuoThreads, 4) void fc_forward_ring_kernel(
             while (s < run_end) {
                 const int m = s & (CR - 1);
                 if (m == 0 && s > 0) {
-                    // entering a chunk: the chunk before it is consumed, its ring slot is refilled nr - 1 chunks ahead
+                    // entering a chunk: the chunk before it is consumed, its ring slot is refilled nr - 1 chunks ahead.  NO wait
+                    // here (ring_landed): the chunk entered was requested at least CR slots of this stream ago
                     const int ch = s >> LOG_CR;
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     if (ch - 1 + nr < nch) dma_chunk(j, beg[j], ch - 1 + nr);
                 }
                 int stop = min(run_end, s - m + CR);                  // the end of this chunk
-                if (nr == 2) {
-                    // the look-ahead of position CR - 2 enters a chunk requested at the last chunk entry
-                    if (m == CR - 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    else if (m < CR - 2) stop = min(stop, s - m + CR - 2);
+                if constexpr (!kLookaheadProven) {
+                    if (nr == 2) {
+                        // the look-ahead of position CR - 2 enters a chunk requested at the last chunk entry, CR - 2 = 2 slots ago: the
+                        // two row requests of those slots are younger than the chunk's, whatever else was requested since
+                        if (m == CR - 2) {
+                            meter.begin();
+                            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                            meter.end(1);
+                        }
+                        else if (m < CR - 2) stop = min(stop, s - m + CR - 2);
+                    }
                 }
                 if ((s & 1) && s < stop) {
                     slot(s, xo);
@@ -382,8 +412,9 @@ __global__ __launch_bounds__(kDuoThreads, 4) void fc_forward_ring_kernel(
             }
             stamp(0);
             if (q == R - 2) {
-                // my targets are done: start streaming the first record chunks of my next tile's targets
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                // my targets are done: start streaming the first record chunks of my next tile's targets (no wait: ring_landed)
+                meter.begin();
+                meter.end(7);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int nnch = (nend[j] - nbeg[j] + CR - 1) >> LOG_CR;
@@ -409,7 +440,13 @@ __global__ __launch_bounds__(kDuoThreads, 4) void fc_forward_ring_kernel(
         flush_row(clo[0], 0);                            // the outermost ring
         if (vt < a.nv_full) flush_row(clo[1], 1);
         __syncthreads();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the next tile's first record chunks have landed)
+        // the next tile's first record chunks have landed: a contracting wavefront has used ring R - 2's filter fragments, which it
+        // requested after them (ring_landed), and keeps ring R - 1's in flight under first_rows; the others have nothing younger to spare
+        if (!mma_active || (a.dbg & 2)) {
+            meter.begin();
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            meter.end(3);
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             beg[j] = nbeg[j];
@@ -454,6 +491,7 @@ __global__ __launch_bounds__(kDuoThreads, 4) void fc_forward_ring_kernel(
     }
     stamp(30);
     stamp.realtime(31);
+    meter.close();
 }
 
 // LDS plan: record chunks per stream (4, else 2) as fit beside slab and partials in half a CU's LDS.
