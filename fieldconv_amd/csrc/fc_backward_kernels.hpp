@@ -491,9 +491,10 @@ __global__ __launch_bounds__(kThreads) void fc_backward_data_kernel(
             if constexpr (SPLIT) vs = (vs == vscale) ? vscale + 2 * kTile : vscale;   // the next group writes the other buffer
         }
         if (e_active && ejn < a.N) {
-            const float q = eq * einv2;                   // (i x / |x|^2) sum_f m Im(conj(gxt_f) xt_f)
-            gxacc.x += -exs.y * q;
-            gxacc.y += exs.x * q;
+            // (i x / |x|^2) sum_f m Im(conj(gxt_f) xt_f) -- x / |x|^2 first: eq / |x|^2 alone is subnormal for a large x beside a small
+            // cotangent, though the term is as large as the first one
+            gxacc.x += (-exs.y * einv2) * eq;
+            gxacc.y += (exs.x * einv2) * eq;
             ggx[(size_t)((gsel << pl) + (tile & ((1 << pl) - 1))) * a.part_stride + (size_t)ejn * I + ei] = gxacc;
         }
         beg = nbeg;

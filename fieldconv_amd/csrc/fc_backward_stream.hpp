@@ -495,7 +495,7 @@ __global__ __launch_bounds__(kThreads) void fc_backward_stream_kernel(
     lds_f16* const xb0 = (lds_f16*)(smem + 2 * a.rec_bytes);          // [2][c_hi, c_lo, d_hi, d_lo][IP][kXbStride] halves: second operand of gW
     char* const xrow0 = smem + 2 * a.rec_bytes + 2 * 4 * xplane * 2;    // [3][16 vertices][I] complex: the x rows of a tile (DMA)
     float* const tail0 = reinterpret_cast<float*>(xrow0 + 3 * xtile);   // [4][64]: [16] s_v, [16] 1/s_v of a record (DMA)
-    float* const pmax0 = tail0 + 4 * 64;                                // [2][8 row pairs][64]  max over the pair of |x[v][i]|^2 / s_v^2
+    float* const pmax0 = tail0 + 4 * 64;                                // [2][8 row pairs][64]  max over the pair of |x[v][i]| / s_v
     float* const tinv0 = pmax0 + 2 * 8 * 64;                            // [2][64]  1 / t[i]
     float* const part0 = tinv0 + 2 * 64;                                // [2][nslots][16][kStreamPartStride]  k-partials of gxt
     const int part_floats = a.nslots * kTile * kStreamPartStride;
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(kThreads) void fc_backward_stream_kernel(
     };
     // Second operand of gW for record k: x~[v][i] / s_v * t[i] in halves, planes [i][vertex], t[i] = power-of-two scale of column i over
     // the tile's vertices -- in two steps, one record apart, so that nobody forms a 16-row maximum alone:
-    //   pair_max(k): my two rows' max of |x|^2 / s_v^2 per column -> pmax
+    //   pair_max(k): my two rows' max of |x| / s_v per column -> pmax
     //   pair_rows(k): t[i] from the eight pair maxima; my two rows rotated, scaled, split and stored as (v, v+1) dwords
     auto pair_max = [&](const int k) {
         if (k >= nrec || op_pair < 0) return;
@@ -566,9 +566,17 @@ __global__ __launch_bounds__(kThreads) void fc_backward_stream_kernel(
         const float* tl = tail0 + (k & 3) * 64 + kTile + 2 * op_pair;
         const int lc = lane < I ? lane : 0;
         const float2 x0 = *reinterpret_cast<const float2*>(rows + lc * 8), x1 = *reinterpret_cast<const float2*>(rows + xrs + lc * 8);
-        const float i0_ = tl[0], i1_ = tl[1];
-        const float m0 = (x0.x * x0.x + x0.y * x0.y) * (i0_ * i0_), m1 = (x1.x * x1.x + x1.y * x1.y) * (i1_ * i1_);
-        pmax0[((k & 1) * 8 + op_pair) * 64 + lane] = lane < I ? fmaxf(m0, m1) : 0.f;
+        // |x| / s_v with no square of a small number: neither |x|^2 (zero below 2^-75) nor (1 / s_v)^2 (zero once the row of H is
+        // below 2^-62) -- the entry is brought to 2^13 by its own power of two first, and the two exponents are folded in behind the
+        // square root (v_sqrt_f32 is good to an ulp; pair_rows adds the margin that keeps the bound above the true value)
+        // (a SUBNORMAL entry keeps scale 1 and its squares flush to zero: it counts as zero for the column bound)
+        auto mag = [](const float2 x, const float inv) {
+            float s, is;
+            split_scale(fmaxf(fabsf(x.x), fabsf(x.y)), s, is);
+            const float xr = x.x * s, xi = x.y * s;
+            return __builtin_amdgcn_sqrtf(xr * xr + xi * xi) * is * inv;
+        };
+        pmax0[((k & 1) * 8 + op_pair) * 64 + lane] = lane < I ? fmaxf(mag(x0, tl[0]), mag(x1, tl[1])) : 0.f;
     };
     const int pm_ = m < 0 ? -m : m;
     auto pair_rows = [&](const int k) {
@@ -588,10 +596,10 @@ __global__ __launch_bounds__(kThreads) void fc_backward_stream_kernel(
             xv[e] = *reinterpret_cast<const float2*>(rows + e * xrs + lc * 8);
             inv[e] = tl[e];
         }
-        float cm2 = 0.f;
+        float cm = 0.f;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) cm2 = fmaxf(cm2, pv[j]);
-        const float cm = __builtin_amdgcn_sqrtf(cm2) * 1.000001f;      // (never below the true value: v_sqrt_f32 is good to an ulp)
+        for (int j = 0; j < 8; ++j) cm = fmaxf(cm, pv[j]);
+        cm *= 1.000001f;                                               // (never below the true value: pair_max is good to two ulps)
         float t, inv_t;
         split_scale(cm, t, inv_t);
         uint32_t hh[2], ll[2];

@@ -307,9 +307,9 @@ __device__ __forceinline__ float2 gx_from_slices(const float2 x, const float2* _
         acc.y += out.y;
         eq += (float)mm * (z[f].x * xtv.y - z[f].y * xtv.x);
     }
-    const float q = eq * inv2;
-    acc.x += -x.y * q;
-    acc.y += x.x * q;
+    // (x / |x|^2 first: eq / |x|^2 alone is subnormal for a large x beside a small cotangent, though the term is as large as the first one)
+    acc.x += (-x.y * inv2) * eq;
+    acc.y += (x.x * inv2) * eq;
     return acc;
 }
 

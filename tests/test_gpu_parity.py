@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _dynamic_range_cases import rowwise_err
 from conftest import load_golden, rel_err
 from oracle import fieldconv_oracle as orc
 
@@ -409,16 +410,6 @@ def test_fieldconv_vs_oracle(case, dev):
     assert rel_err(H(y), y_ref) < TOL
     assert rel_err(H(gx), gx_ref) < TOL
     assert rel_err(H(gW), gW_ref) < TOL
-
-
-def rowwise_err(a, ref):
-    """max over rows of max|delta_row| / max|ref_row| (rows of zeros in ref must be exactly zero)."""
-    a, ref = np.asarray(a), np.asarray(ref)
-    a, ref = a.reshape(a.shape[0], -1), ref.reshape(ref.shape[0], -1)
-    num = np.abs(a - ref).max(axis=1)
-    den = np.abs(ref).max(axis=1)
-    assert np.all(num[den == 0] == 0)
-    return float((num[den > 0] / den[den > 0]).max())
 
 
 @pytest.mark.parametrize('global_scale', [1.0, 1e-18, 1e12], ids=['unit', 'tiny', 'huge'])
