@@ -230,6 +230,7 @@ SIGNATURES = {
                                  _c_int32, ctypes.c_float, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _c_int32, _vp, _sz, _vp]),
     'fc_mesh_diagonals': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp, _c_int32, _vp, _vp, _vp, _vp]),
     'fc_mesh_graph_merge': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp, _vp, _vp, _vp]),
+    'fc_transfer': (ctypes.c_int, [_vp] * 5 + [_c_int32] * 7 + [_vp, _vp]),
 }
 
 _LIB = None

@@ -1212,3 +1212,4 @@ from .geodesic import (compose_map, correspondence_curve, geodesic_distances, ge
 from .geodesic_sampling import (geodesic_farthest_point_sample, geodesic_farthest_point_sample_batched,          # noqa: E402,F401  (csrc/fc_geodesic_fps.hip)
                                 geodesic_radius_edges)
 from .logmap import log_map_transport, vertex_frames          # noqa: E402,F401  (csrc/fc_logmap.hip)
+from .transfer import TransferPlan, level_transfer, sample_cells, tangent_transfer          # noqa: E402,F401  (csrc/fc_transfer.hip)

@@ -13,7 +13,8 @@ from .twin_eval import TwinEval
 from .mesh_pool import MeshPool
 from .linear_cross_entropy import LinearCrossEntropy
 from ..head import vertex_accuracy
+from .tangent_pool import TangentPool, TangentUnpool
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
            'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval',
-           'LinearCrossEntropy', 'vertex_accuracy', 'MeshPool']
+           'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'MeshPool']

@@ -1,0 +1,291 @@
+"""Tangent-feature pooling and unpooling between two sample levels (csrc/fc_transfer.hip): a sparse complex transfer
+
+    y[o, c] = sum over the rows e with out(e) = o of  coef[e] * x[in(e), c]
+
+with a deterministic gradient, the plan that holds its two CSRs, and the glue that builds the plans of a level pair from the
+package's own geodesics: nearest-sample cells (geodesic.nearest_sample), sample masses (data.w) and the transport phase along a
+shortest-path tree (logmap.log_map_transport).
+
+A tangent-vector feature lives in its sample's frame, so a plain mean over a cell is wrong: every term is parallel-transported
+into the receiving sample's frame first, which is a multiplication by a unit complex number -- the phase of a row.  Real
+(scalar) features, such as ECHOBlock descriptors and logits, are resampled with the weights alone.
+
+Features are (N,C) tensors on a ROCm device; there is no CPU or eager path: a CPU feature tensor raises.  The geometry (plans,
+cells) is built on the device whatever device its inputs are on.  Bad arguments raise ValueError before anything is launched.
+weight and phase are geometry: they never receive a gradient."""
+import torch
+
+from . import _lib
+from .geodesic import _check_diagonals, _check_index, _check_mesh, _device_of, _ptr, _segment_sum, _stream, mesh_edge_graph, nearest_sample
+from .logmap import _check_bound, log_map_transport
+from .pooling import check_ptr
+
+_DTYPES = {torch.float32: (0, 0), torch.float64: (1, 0), torch.complex64: (0, 1), torch.complex128: (1, 1)}          # (fc_dtype, is_complex)
+_REAL = (torch.float32, torch.float64)
+_COMPLEX = {torch.float32: torch.complex64, torch.float64: torch.complex128}
+
+
+class _Csr(object):
+    """One CSR by output row on the device: rowptr (n_rows+1,) int32, col (E,) int32, weight (E,) and phase (E,) or None in slot
+    order; the casts of weight and phase to a feature's scalar type are made once and kept."""
+
+    def __init__(self, rowptr, col, weight, phase):
+        self.rowptr, self.col, self.weight, self.phase = rowptr, col, weight, phase
+        self._cast = {}
+
+    def coefficients(self, real):
+        if real not in self._cast:
+            self._cast[real] = (self.weight.to(real).contiguous(),
+                                None if self.phase is None else self.phase.to(_COMPLEX[real]).contiguous())
+        return self._cast[real]
+
+
+def _whole(v, what, name):
+    try:
+        ok = not isinstance(v, bool) and int(v) == v and 0 <= v < 2 ** 31 - 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'{what}: {name} must be an integer in [0, 2^31 - 1), got {v!r}')
+    return int(v)
+
+
+class TransferPlan(object):
+    """The sparse matrix T (n_out x n_in) of a transfer y = T x, T[out, in] = the sum of the coefficients of the rows [out, in].
+
+    rows    (E,2) int64 [out, in], in any order; duplicates add
+    weight  (E,) float32 or float64
+    phase   (E,) complex64 or complex128, or None for 1
+    conj_phase      the coefficient of a row is weight * conj(phase) in place of weight * phase (complex features; real
+                    features always take the weight alone)
+
+    Ranges, dtypes and lengths are checked (ValueError) before anything touches the device.  The rows are grouped by `out` with
+    a stable sort -- a row's terms are added in the order the caller gave them -- and the transposed CSR, which the gradient
+    runs on, is built from that order by a second stable sort: both once, both kept on the device (rows.device when that is a
+    ROCm device, else the current one).  adjoint() is the plan of the conjugate-transposed matrix; it shares every buffer."""
+
+    def __init__(self, rows, weight, phase=None, n_out=None, n_in=None, conj_phase=False):
+        what = 'TransferPlan'
+        if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != 2 or rows.dtype != torch.int64:
+            raise ValueError(f'{what}: rows must be an (E,2) int64 tensor, got '
+                             f'{(tuple(rows.shape), rows.dtype) if torch.is_tensor(rows) else type(rows).__name__}')
+        E = int(rows.shape[0])
+        if not torch.is_tensor(weight) or weight.dtype not in _REAL:
+            raise ValueError(f'{what}: weight must be a float32 or float64 tensor, got '
+                             f'{weight.dtype if torch.is_tensor(weight) else type(weight).__name__}')
+        if tuple(weight.shape) != (E,):
+            raise ValueError(f'{what}: weight must have one entry per row, ({E},), got {tuple(weight.shape)}')
+        if phase is not None:
+            if not torch.is_tensor(phase) or phase.dtype not in (torch.complex64, torch.complex128):
+                raise ValueError(f'{what}: phase must be a complex64 or complex128 tensor or None, got '
+                                 f'{phase.dtype if torch.is_tensor(phase) else type(phase).__name__}')
+            if tuple(phase.shape) != (E,):
+                raise ValueError(f'{what}: phase must have one entry per row, ({E},), got {tuple(phase.shape)}')
+        if n_out is None or n_in is None:
+            raise ValueError(f'{what}: n_out and n_in, the numbers of output and input rows, must be given')
+        n_out, n_in = _whole(n_out, what, 'n_out'), _whole(n_in, what, 'n_in')
+        if E >= 2 ** 31 - 1:
+            raise ValueError(f'{what}: slots are 32-bit indices in the kernel: at most 2^31 - 2 rows, got {E}')
+        if not isinstance(conj_phase, bool):
+            raise ValueError(f'{what}: conj_phase must be True or False, got {conj_phase!r}')
+        if E:
+            lo, hi = rows.min(0).values.tolist(), rows.max(0).values.tolist()
+            if lo[0] < 0 or hi[0] >= n_out:
+                raise ValueError(f'{what}: rows[:, 0] must lie in [0, {n_out}), got values from {lo[0]} to {hi[0]}')
+            if lo[1] < 0 or hi[1] >= n_in:
+                raise ValueError(f'{what}: rows[:, 1] must lie in [0, {n_in}), got values from {lo[1]} to {hi[1]}')
+        dev = _device_of(rows)
+        with torch.cuda.device(dev):
+            r = rows.detach().to(dev)
+            w = weight.detach().to(dev)
+            ph = None if phase is None else phase.detach().to(dev).resolve_conj()
+            order = torch.sort(r[:, 0], stable=True)
+            out_sorted, by_out = order.values.contiguous(), order.indices
+            col = r[by_out, 1].contiguous()
+            w, ph = w[by_out].contiguous(), None if ph is None else ph[by_out].contiguous()
+            fwd = _Csr(torch.searchsorted(out_sorted, torch.arange(n_out + 1, device=dev)).to(torch.int32), col.to(torch.int32), w, ph)
+            order = torch.sort(col, stable=True)          # the transposed matrix: grouped by `in`, a row's slots in the order above
+            in_sorted, by_in = order.values.contiguous(), order.indices
+            bwd = _Csr(torch.searchsorted(in_sorted, torch.arange(n_in + 1, device=dev)).to(torch.int32),
+                       out_sorted[by_in].to(torch.int32).contiguous(), w[by_in].contiguous(), None if ph is None else ph[by_in].contiguous())
+        self._set(fwd, bwd, n_out, n_in, E, conj_phase, dev)
+
+    def _set(self, fwd, bwd, n_out, n_in, n_rows, conj_phase, device):
+        self._fwd, self._bwd, self.n_out, self.n_in, self.n_rows, self.conj_phase, self.device = fwd, bwd, n_out, n_in, n_rows, conj_phase, device
+        return self
+
+    def adjoint(self):
+        """The plan of T^H (n_in x n_out): the two CSRs swapped and the conjugate flag flipped; no copy."""
+        return TransferPlan.__new__(TransferPlan)._set(self._bwd, self._fwd, self.n_in, self.n_out, self.n_rows, not self.conj_phase,
+                                                        self.device)
+
+    def rows(self):
+        """(rows (E,2) int64 [out, in], weight (E,), phase (E,) or None) in slot order: grouped by out, the caller's order within
+        a group; phase as given (conj_phase is not applied)."""
+        c = self._fwd
+        counts = (c.rowptr[1:] - c.rowptr[:-1]).to(torch.int64)
+        out = torch.repeat_interleave(torch.arange(self.n_out, device=self.device), counts)
+        return torch.stack((out, c.col.to(torch.int64)), 1), c.weight, c.phase
+
+    def __repr__(self):
+        return 'TransferPlan(n_out={}, n_in={}, rows={}{})'.format(self.n_out, self.n_in, self.n_rows, ', conj_phase=True' if self.conj_phase else '')
+
+
+def _launch(x, plan):
+    """y = T x of a checked, contiguous device tensor"""
+    lib = _lib.load()
+    dt, cplx = _DTYPES[x.dtype]
+    C = int(x.shape[1])
+    csr = plan._fwd
+    w, ph = csr.coefficients(_REAL[dt])
+    with torch.cuda.device(x.device):
+        y = torch.empty((plan.n_out, C), dtype=x.dtype, device=x.device)
+        _lib.check(lib.fc_transfer(_ptr(x), _ptr(csr.rowptr), _ptr(csr.col), _ptr(w), _ptr(ph) if cplx else None, int(plan.conj_phase and cplx),
+                                   plan.n_out, plan.n_in, plan.n_rows, C, dt, cplx, _ptr(y), _stream()), 'fc_transfer')
+    return y
+
+
+class _TangentTransfer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, plan):
+        ctx.plan = plan
+        return _launch(x.detach().resolve_conj().resolve_neg().contiguous(), plan)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        plan = ctx.plan
+        g = g.detach().resolve_conj().resolve_neg().contiguous()
+        return _launch(g, plan.adjoint()), None          # d/dx of Re<gy, T x> is T^H gy: the same kernel on the transposed CSR
+
+
+def tangent_transfer(x, plan):
+    """y (n_out, C) = T x for x (n_in, C) complex64 / complex128 (coefficient weight * phase, or weight * conj(phase) for a plan
+    with conj_phase) or float32 / float64 (coefficient weight), on the plan's ROCm device.  One launch, no atomics: a row's terms
+    are added in the plan's slot order, two runs give the same bits, a row without terms is exactly zero.  Gradient flows to x
+    only (the same kernel on plan.adjoint(), as deterministic as the forward pass), and only when x requires one.  A
+    non-contiguous x is made contiguous."""
+    what = 'tangent_transfer'
+    if not isinstance(plan, TransferPlan):
+        raise ValueError(f'{what}: plan must be a TransferPlan, got {type(plan).__name__}')
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError(f'{what}: x must be an (n_in, C) tensor, got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}')
+    if x.dtype not in _DTYPES:
+        raise TypeError(f'{what}: x is {x.dtype}; complex64, float32, complex128 and float64 are implemented')
+    if not x.is_cuda:
+        raise RuntimeError(f'{what}: x is on {x.device}; the transfer runs on a ROCm device and has no CPU path')
+    if x.device != plan.device:
+        raise RuntimeError(f'{what}: x is on {x.device}, the plan on {plan.device}')
+    if int(x.shape[0]) != plan.n_in or int(x.shape[1]) < 1:
+        raise ValueError(f'{what}: x must be ({plan.n_in}, C) with C >= 1 for this plan, got {tuple(x.shape)}')
+    if plan.n_out * int(x.shape[1]) >= 2 ** 40 or int(x.shape[1]) >= 2 ** 31:
+        raise ValueError(f'{what}: n_out * C must stay below 2^40, got {plan.n_out} x {int(x.shape[1])}')
+    return _TangentTransfer.apply(x, plan)
+
+
+# ------------------------------------------------------------------ building a level pair
+def _check_coarse(coarse, S, what):
+    """(S_c,) int64 strictly ascending positions in [0,S) -> its entries as Python ints"""
+    _check_index(coarse, S, what, 'coarse')
+    host = coarse.tolist()
+    if any(b <= a for a, b in zip(host, host[1:])):
+        raise ValueError(f'{what}: coarse must be strictly ascending positions in sample_idx')
+    return host
+
+
+def _check_batch(pos_ptr, ptr, coarse_ptr, V, S, host_c, what):
+    """all three range tables or none -> (host pos_ptr, host ptr, host coarse_ptr) or (None, None, None)"""
+    given = [t is not None for t in (pos_ptr, ptr, coarse_ptr)]
+    if any(given) and not all(given):
+        raise ValueError(f'{what}: pos_ptr, ptr and coarse_ptr go together (the ranges of a MeshBatch and of its coarse level): give all or none')
+    if not any(given):
+        return None, None, None
+    hp, hs, hc = check_ptr(pos_ptr, V, what, 'pos_ptr'), check_ptr(ptr, S, what, 'ptr'), check_ptr(coarse_ptr, len(host_c), what, 'coarse_ptr')
+    if not len(hp) == len(hs) == len(hc):
+        raise ValueError(f'{what}: pos_ptr, ptr and coarse_ptr describe {len(hp) - 1}, {len(hs) - 1} and {len(hc) - 1} meshes')
+    for b in range(len(hp) - 1):
+        mine = host_c[hc[b]:hc[b + 1]]
+        if not mine:
+            raise ValueError(f'{what}: mesh {b} of the batch has no coarse samples')
+        if mine[0] < hs[b] or mine[-1] >= hs[b + 1]:
+            raise ValueError(f'{what}: the coarse samples of mesh {b} must be positions inside its own range [{hs[b]}, {hs[b + 1]}) of sample_idx')
+    return hp, hs, hc
+
+
+def sample_cells(pos, face, sample_idx, coarse, graph=None, diagonals=False, pos_ptr=None, ptr=None, coarse_ptr=None):
+    """(cell (S_f,) int64, dist (S_f,) float32): which coarse sample every fine sample belongs to.  sample_idx (S_f,) int64
+    are the fine samples (vertices of pos), coarse (S_c,) int64 strictly ascending POSITIONS in sample_idx.  cell[f] is the
+    nearest_sample label of vertex sample_idx[f] among the vertices sample_idx[coarse] -- a position in coarse, -1 where no
+    coarse sample is reachable -- and dist[f] its edge-graph distance (+inf there).  A pure composition of nearest_sample: its
+    bits, its tie rule (the lower position), its graph= and diagonals=.  A coarse sample is in its own cell, at distance 0,
+    unless a fine sample listed earlier names the same vertex.
+    pos_ptr, ptr, coarse_ptr: all None, or the (B+1,) int64 range tables of a MeshBatch over pos, sample_idx and coarse: every
+    mesh searches its own coarse samples only, so no cell crosses meshes."""
+    what = 'sample_cells'
+    _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
+    V = int(pos.shape[0])
+    _check_index(sample_idx, V, what, 'sample_idx')
+    host_c = _check_coarse(coarse, int(sample_idx.numel()), what)
+    hp, hs, hc = _check_batch(pos_ptr, ptr, coarse_ptr, V, int(sample_idx.numel()), host_c, what)
+    fine = sample_idx.to(pos.device)
+    label, dist = nearest_sample(pos, face, fine[coarse.to(pos.device)], pos_ptr, coarse_ptr, graph=graph, diagonals=diagonals)
+    return label[fine], dist[fine]
+
+
+def level_transfer(pos, face, sample_idx, coarse, w_fine, graph=None, diagonals=False, pos_ptr=None, ptr=None, coarse_ptr=None, bound=None,
+                   return_cells=False):
+    """(pool_plan, unpool_plan) between the fine samples sample_idx (S_f,) and the coarse samples sample_idx[coarse] (S_c,);
+    with return_cells also (cell, n_outside): sample_cells' labels and the number of fine samples in no cell.
+
+    For a fine sample f with cell c >= 0 and a = coarse[c], the row [a, f] goes through log_map_transport(pos, face, sample_idx,
+    rows, bound): its xp turns coordinates in a's frame into coordinates in f's frame after transport along the shortest-path
+    tree of a.  bound defaults to the largest finite cell distance moved one float32 step upward, so that the strict threshold
+    of the tree reaches every member of every cell; when that distance is 0 no tree is grown and every phase is 1.
+      unpool  (S_f x S_c)  row [f, c], weight 1, phase xp: a coarse feature carried out to the members of its cell.
+      pool    (S_c x S_f)  row [c, f], weight w_fine[f] / W_c with W_c the float32 sum of the cell's w_fine in ascending f (1 / n_c
+                           for a cell of n_c members where W_c == 0), phase conj(xp): the mass-weighted mean of the cell in a's
+                           frame.  The weights of a non-empty cell sum to 1, so pool(unpool(y)) = y.
+    A fine sample with cell -1 belongs to no cell: pooling ignores it and unpooling gives it zero.
+    w_fine: (S_f,) or (S_f,1) float32, the fine level's data.w.  graph, diagonals, pos_ptr / ptr / coarse_ptr: as in
+    sample_cells (one graph is built and shared by both steps).  Plans live on the device; nothing here is differentiable."""
+    what = 'level_transfer'
+    _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
+    V = int(pos.shape[0])
+    _check_index(sample_idx, V, what, 'sample_idx')
+    S_f = int(sample_idx.numel())
+    host_c = _check_coarse(coarse, S_f, what)
+    S_c = len(host_c)
+    _check_batch(pos_ptr, ptr, coarse_ptr, V, S_f, host_c, what)
+    if not torch.is_tensor(w_fine) or w_fine.dtype != torch.float32 or tuple(w_fine.shape) not in ((S_f,), (S_f, 1)):
+        raise ValueError(f'{what}: w_fine must be an ({S_f},) or ({S_f},1) float32 tensor, got '
+                         f'{(tuple(w_fine.shape), w_fine.dtype) if torch.is_tensor(w_fine) else type(w_fine).__name__}')
+    if bound is not None:
+        bound = _check_bound(bound, what)
+    dev = _device_of(pos)
+    if graph is None:
+        graph = mesh_edge_graph(pos, face, diagonals)
+    cell, dist = sample_cells(pos, face, sample_idx, coarse, graph=graph, pos_ptr=pos_ptr, ptr=ptr, coarse_ptr=coarse_ptr)
+    with torch.cuda.device(dev):
+        cell, dist = cell.to(dev), dist.to(dev)
+        member = torch.nonzero(cell >= 0)[:, 0]          # ascending f
+        c = cell[member]
+        n_outside = S_f - int(member.numel())
+        a = coarse.to(dev)[c]
+        if bound is None:
+            far = float(dist[member].max()) if member.numel() else 0.0
+            bound = float(torch.nextafter(torch.tensor(far, dtype=torch.float32), torch.tensor(float('inf'), dtype=torch.float32))) if far > 0 else None
+        if bound is None or not member.numel():
+            xp = torch.ones(int(member.numel()), dtype=torch.complex64, device=dev)
+        else:
+            xp = log_map_transport(pos, face, sample_idx, torch.stack((a, member), 1), bound, graph=graph,
+                                   pos_ptr=pos_ptr, ptr=ptr)[2].to(dev)
+        w = w_fine.detach().to(dev).reshape(-1).contiguous()
+        total = _segment_sum(w, cell, S_c, 1.0, dev)          # float32, ascending f; cell -1 contributes to nothing
+        count = torch.bincount(c, minlength=S_c).to(torch.float32)
+        weight = torch.where(total[c] == 0, 1.0 / count[c], w[member] / total[c])
+        unpool = TransferPlan(torch.stack((member, c), 1), torch.ones_like(weight), xp, n_out=S_f, n_in=S_c)
+        pool = TransferPlan(torch.stack((c, member), 1), weight, xp, n_out=S_c, n_in=S_f, conj_phase=True)
+    return (pool, unpool, cell.to(pos.device), n_outside) if return_cells else (pool, unpool)

@@ -871,6 +871,19 @@ int fc_mesh_diagonals(const float* pos, const int64_t* face, int32_t V, int32_t 
 int fc_mesh_graph_merge(const int64_t* key, const float* length, int32_t N, int32_t V, uint8_t* head, int32_t* src, int32_t* nbr,
                         float* out_length, void* stream);
 
+/* ---- sparse transfer between two sample levels: tangent-feature pooling and unpooling (csrc/fc_transfer.hip) ------------------- *
+ *   y[o, c] = sum over the slots e in [rowptr[o], rowptr[o+1]) of coef[e] * x[col[e], c]
+ * x (n_in, C) and y (n_out, C) row-major, dtype FC_F32 / FC_F64, is_complex 1 (interleaved pairs: complex64 / complex128) or 0
+ * (float32 / float64).  rowptr (n_out+1) / col (n_slots) int32: a CSR by OUTPUT row.  weight (n_slots) real and phase (n_slots)
+ * complex (interleaved), both of x's scalar type; phase may be NULL (1 everywhere).  Complex x: coef = weight * phase, or
+ * weight * conj(phase) when conj_phase is 1.  Real x: coef = weight; phase and conj_phase are not read.
+ * One lane owns one piece of 8 bytes or more of an output row and adds the row's terms to a zero in ascending slot order: no
+ * atomics, the same bits on every run, a row without slots is written as zero.  The gradient to x is the same call on the
+ * transposed CSR with conj_phase flipped.  rowptr entries are clamped to [0, n_slots]; a slot whose col lies outside [0, n_in)
+ * contributes nothing and reads nothing.  C >= 1 is arbitrary.  No workspace, no allocation or synchronisation inside. */
+int fc_transfer(const void* x, const int32_t* rowptr, const int32_t* col, const void* weight, const void* phase, int32_t conj_phase,
+                int32_t n_out, int32_t n_in, int32_t n_slots, int32_t C, int32_t dtype, int32_t is_complex, void* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
