@@ -5,30 +5,20 @@
 //   fc_geodesic_nearest          one multi-source problem per mesh of a mini-batch -> (V) distances and nearest-source labels;
 //   fc_face_areas, fc_segment_sum_f32      triangle areas and sums over consecutive ranges in a fixed order (the lumped vertex
 //                                mass and its sum onto the nearest sample: no float atomics, the same bits on every run).
-// One solver kernel serves both launch shapes.  A workgroup of 1024 threads owns one problem: thread t owns the vertices
-// t, t + 1024, ... of the problem's range, pulls d[v] = min(d[v], fl32(d[u] + len(u,v))) over their CSR rows and writes only its
-// own entries.  Reads of neighbours may be stale: every value ever written is the rounded length of some path from a source,
-// an upper bound of the least fixpoint, and fl32(a + l) is monotone in a, so the least fixpoint is the only state in which a
-// whole sweep changes nothing -- whatever the order of the relaxations.  A sweep sees at least everything the previous sweep
-// wrote (the barrier), so at most n sweeps change something.  Labels are propagated afterwards over the fixed set of tight
-// edges fl32(d[u] + len) == d[v]: a second min-propagation with the same structure.  No atomics, nothing crosses a workgroup.
+// One solver kernel serves both launch shapes, one workgroup per problem, sweeping every vertex of the range until a sweep
+// changes nothing: the least fixpoint whatever the schedule (header of fc_geodesic_relax.hpp, which also holds the ranges and
+// the launch).  Labels are propagated afterwards over the fixed set of tight edges fl32(d[u] + len) == d[v]: a second
+// min-propagation with the same structure.  No atomics, nothing crosses a workgroup.
 #include <limits.h>
 #include "../../include/fieldconv_hip.h"
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_geodesic_relax.hpp"
 
 namespace fc {
 
-constexpr int kGeoThreads = 1024;
-// Vertices of a range whose distances (float) AND labels (int32) live in LDS: 8 B each, 160 000 B of the CU's 163 840; the
-// workgroup reduction of __syncthreads_or takes 256 B of static LDS beside them.
-constexpr int kGeoLdsVertices = 20000;
-
 struct geo_args {
-    const int32_t* rowptr;       // (V+1) CSR over the vertices of all meshes
-    const int32_t* nbr;          // (E)
-    const float* len;            // (E)
-    int32_t V, E;
+    gf_graph g;
     const int64_t* pos_ptr;      // null: every problem spans [0,V); else problem p spans [pos_ptr[p], pos_ptr[p+1])
     const int64_t* sources;      // vertex numbers
     const int64_t* src_ptr;      // null: problem p has sources[p * sources_each .. (p+1) * sources_each); else
@@ -42,24 +32,18 @@ struct geo_args {
     int32_t lds_vertices;        // ranges of at most this many vertices belong to the LDS instantiation, larger ones to the other
 };
 
-__device__ __forceinline__ int64_t geo_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 template <bool kLds>
-__global__ __launch_bounds__(kGeoThreads) void geodesic_kernel(const geo_args a) {
+__global__ __launch_bounds__(kGfThreads) void geodesic_kernel(const geo_args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int p = blockIdx.x, t = threadIdx.x;
     // whatever the tables hold, a problem reads and writes inside [0,V) and [0,n_sources) only
-    int v0 = 0, v1 = a.V;
-    if (a.pos_ptr) {
-        v0 = (int)geo_clamp(a.pos_ptr[p], 0, a.V);
-        v1 = (int)geo_clamp(a.pos_ptr[p + 1], v0, a.V);
-    }
-    const int n = v1 - v0;
+    int v0, n;
+    gf_mesh_range(a.pos_ptr, p, a.g.V, v0, n);
     if ((n <= a.lds_vertices) != kLds) return;          // (uniform over the workgroup) the other instantiation's problem
-    int64_t s0 = geo_clamp(p * a.sources_each, 0, a.n_sources), s1 = geo_clamp(s0 + a.sources_each, s0, a.n_sources);
+    int64_t s0 = gf_clamp(p * a.sources_each, 0, a.n_sources), s1 = gf_clamp(s0 + a.sources_each, s0, a.n_sources);
     if (a.src_ptr) {
-        s0 = geo_clamp(a.src_ptr[p], 0, a.n_sources);
-        s1 = geo_clamp(a.src_ptr[p + 1], s0, a.n_sources);
+        s0 = gf_clamp(a.src_ptr[p], 0, a.n_sources);
+        s1 = gf_clamp(a.src_ptr[p + 1], s0, a.n_sources);
     }
     const bool want_label = a.label != nullptr;
     float* const row = a.dist + (int64_t)p * a.dist_stride + v0;
@@ -67,14 +51,14 @@ __global__ __launch_bounds__(kGeoThreads) void geodesic_kernel(const geo_args a)
     int32_t* const lab = kLds ? reinterpret_cast<int32_t*>(smem) + a.lds_vertices : a.label_ws + v0;
     const float inf = __int_as_float(0x7f800000);
 
-    for (int i = t; i < n; i += kGeoThreads) {
+    for (int i = t; i < n; i += kGfThreads) {
         d[i] = inf;
         if (want_label) lab[i] = INT_MAX;
     }
     // every thread walks the source list and takes the sources it owns: positions ascend, so the first hit is the lowest
     for (int64_t q = s0; q < s1; ++q) {
         const int64_t s = a.sources[q] - v0;
-        if (s >= 0 && s < n && (int)(s % kGeoThreads) == t) {
+        if (s >= 0 && s < n && (int)(s % kGfThreads) == t) {
             d[s] = 0.f;
             if (want_label && lab[s] == INT_MAX) lab[s] = (int32_t)q;
         }
@@ -84,15 +68,15 @@ __global__ __launch_bounds__(kGeoThreads) void geodesic_kernel(const geo_args a)
     int sw = 0, lsw = 0;
     for (;;) {
         int changed = 0;
-        for (int i = t; i < n; i += kGeoThreads) {
-            const int v = v0 + i;
-            const int e0 = max(a.rowptr[v], 0), e1 = min(a.rowptr[v + 1], a.E);
+        for (int i = t; i < n; i += kGfThreads) {
+            int e0, e1;
+            gf_row(a.g, v0 + i, e0, e1);
             const float old = d[i];
             float best = old;
             for (int e = e0; e < e1; ++e) {
-                const int u = a.nbr[e] - v0;
+                const int u = a.g.nbr[e] - v0;
                 if ((unsigned)u < (unsigned)n) {
-                    const float c = d[u] + a.len[e];
+                    const float c = d[u] + a.g.len[e];
                     best = c < best ? c : best;
                 }
             }
@@ -107,16 +91,16 @@ __global__ __launch_bounds__(kGeoThreads) void geodesic_kernel(const geo_args a)
     if (want_label) {
         for (;;) {
             int changed = 0;
-            for (int i = t; i < n; i += kGeoThreads) {
+            for (int i = t; i < n; i += kGfThreads) {
                 const float dv = d[i];
                 if (!(dv < inf)) continue;          // unreachable: inf + len == inf is no tight edge
-                const int v = v0 + i;
-                const int e0 = max(a.rowptr[v], 0), e1 = min(a.rowptr[v + 1], a.E);
+                int e0, e1;
+                gf_row(a.g, v0 + i, e0, e1);
                 const int32_t old = lab[i];
                 int32_t best = old;
                 for (int e = e0; e < e1; ++e) {
-                    const int u = a.nbr[e] - v0;
-                    if ((unsigned)u < (unsigned)n && d[u] + a.len[e] == dv) {
+                    const int u = a.g.nbr[e] - v0;
+                    if ((unsigned)u < (unsigned)n && d[u] + a.g.len[e] == dv) {
                         const int32_t l = lab[u];
                         best = l < best ? l : best;
                     }
@@ -130,7 +114,7 @@ __global__ __launch_bounds__(kGeoThreads) void geodesic_kernel(const geo_args a)
             if (!__syncthreads_or(changed) || lsw > n) break;
         }
     }
-    for (int i = t; i < n; i += kGeoThreads) {
+    for (int i = t; i < n; i += kGfThreads) {
         if (kLds) row[i] = d[i];
         if (want_label) {
             const int32_t l = lab[i];
@@ -181,7 +165,7 @@ __global__ void segment_sum_kernel(const float* __restrict__ x, const int64_t* _
                                    float* __restrict__ out) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= K) return;
-    const int64_t b = geo_clamp(ptr[k], 0, N), e = geo_clamp(ptr[k + 1], b, N);
+    const int64_t b = gf_clamp(ptr[k], 0, N), e = gf_clamp(ptr[k + 1], b, N);
     float s = 0.f;
     for (int64_t i = b; i < e; ++i) s += x[i];
     out[k] = s / divisor;          // (IEEE division: hipcc's default for float32)
@@ -192,36 +176,17 @@ __global__ void segment_sum_kernel(const float* __restrict__ x, const int64_t* _
 namespace {
 
 int geo_launch(const fc::geo_args& a, int problems, int max_range, bool labels, hipStream_t s) {
-    static bool lds_ok[fc::kMaxDevices] = {};          // (dynamic LDS above 64 KiB has to be allowed once per device)
+    static bool lds_ok[fc::kMaxDevices] = {};
     const size_t per_vertex = labels ? 8 : 4;
-    fc::geo_args b = a;
-    b.lds_vertices = max_range <= fc::kGeoLdsVertices ? max_range : (a.pos_ptr ? fc::kGeoLdsVertices : 0);
-    if (b.lds_vertices > 0) {
-        const size_t lds = per_vertex * (size_t)b.lds_vertices;
-        int dev = 0;
-        if (lds > 64 * 1024 && (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= fc::kMaxDevices)) return FC_ERR_LAUNCH;
-        if (lds > 64 * 1024 && !lds_ok[dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&fc::geodesic_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    8 * fc::kGeoLdsVertices) != hipSuccess)
-                return FC_ERR_LAUNCH;
-            lds_ok[dev] = true;
-        }
-        hipLaunchKernelGGL(fc::geodesic_kernel<true>, dim3((unsigned)problems), dim3(fc::kGeoThreads), lds, s, b);
-    }
-    if (max_range > fc::kGeoLdsVertices)
-        hipLaunchKernelGGL(fc::geodesic_kernel<false>, dim3((unsigned)problems), dim3(fc::kGeoThreads), 0, s, b);
-    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
-}
-
-bool geo_graph_ok(const int32_t* rowptr, const int32_t* nbr, const float* len, int32_t V, int32_t E) {
-    return rowptr && V >= 1 && E >= 0 && (E == 0 || (nbr && len));
+    return fc::gf_launch_pair(fc::geodesic_kernel<true>, fc::geodesic_kernel<false>, a, (unsigned)problems, max_range, a.pos_ptr != nullptr,
+                              [=](size_t n) { return per_vertex * n; }, 8 * (size_t)fc::kGfLdsVertices, 0, lds_ok, s);
 }
 
 }  // namespace
 
 extern "C" {
 
-int32_t fc_geodesic_lds_vertices(void) { return fc::kGeoLdsVertices; }
+int32_t fc_geodesic_lds_vertices(void) { return fc::kGfLdsVertices; }
 
 int fc_mesh_edge_lengths(const float* pos, const int32_t* src, const int32_t* nbr, int32_t V, int32_t E, float* length, void* stream) {
     if (V < 1 || E < 0 || !pos) return FC_ERR_BAD_ARGUMENT;
@@ -252,10 +217,10 @@ int fc_segment_sum_f32(const float* x, const int64_t* ptr, int64_t N, int32_t K,
 
 int fc_geodesic_rows(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* sources, int32_t S,
                      float* dist, int32_t* sweeps, void* stream) {
-    if (!geo_graph_ok(rowptr, nbr, length, V, E) || S < 0 || (S > 0 && (!sources || !dist))) return FC_ERR_BAD_ARGUMENT;
+    if (!fc::gf_graph_ok(rowptr, nbr, length, V, E) || S < 0 || (S > 0 && (!sources || !dist))) return FC_ERR_BAD_ARGUMENT;
     if (S == 0) return FC_OK;
     fc::geo_args a = {};
-    a.rowptr = rowptr, a.nbr = nbr, a.len = length, a.V = V, a.E = E;
+    a.g = {rowptr, nbr, length, V, E};
     a.sources = sources, a.sources_each = 1, a.n_sources = S;
     a.dist = dist, a.dist_stride = V;
     a.sweeps = sweeps;
@@ -263,19 +228,17 @@ int fc_geodesic_rows(const int32_t* rowptr, const int32_t* nbr, const float* len
 }
 
 size_t fc_geodesic_workspace_bytes(int32_t V, int32_t max_range) {
-    return V > 0 && max_range > fc::kGeoLdsVertices ? sizeof(int32_t) * (size_t)V : 0;
+    return V > 0 && max_range > fc::kGfLdsVertices ? sizeof(int32_t) * (size_t)V : 0;
 }
 
 int fc_geodesic_nearest(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
                         const int64_t* sources, const int64_t* src_ptr, int32_t S, int32_t B, int32_t max_range, float* dist,
                         int64_t* label, int32_t* sweeps, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!geo_graph_ok(rowptr, nbr, length, V, E) || S < 1 || B < 1 || !sources || !dist || !label || max_range < 0 || max_range > V)
+    if (!fc::gf_graph_ok(rowptr, nbr, length, V, E) || !fc::gf_batch_ok(pos_ptr, src_ptr, B, max_range, V, S, 0, S) || !sources || !dist || !label)
         return FC_ERR_BAD_ARGUMENT;
-    if ((pos_ptr == nullptr) != (src_ptr == nullptr) || (!pos_ptr && (B != 1 || max_range != V))) return FC_ERR_BAD_ARGUMENT;
-    const size_t need = fc_geodesic_workspace_bytes(V, max_range);
-    if (need && (!workspace || workspace_bytes < need)) return FC_ERR_WORKSPACE;
+    if (!fc::gf_workspace_ok(fc_geodesic_workspace_bytes(V, max_range), workspace, workspace_bytes)) return FC_ERR_WORKSPACE;
     fc::geo_args a = {};
-    a.rowptr = rowptr, a.nbr = nbr, a.len = length, a.V = V, a.E = E;
+    a.g = {rowptr, nbr, length, V, E};
     a.pos_ptr = pos_ptr, a.sources = sources, a.src_ptr = src_ptr, a.sources_each = S, a.n_sources = S;          // (no tables: one problem, every source)
     a.dist = dist, a.dist_stride = 0;
     a.label = label, a.label_ws = static_cast<int32_t*>(workspace), a.sweeps = sweeps;

@@ -3,21 +3,9 @@
 //                                yet taken, d[new] = 0, relaxation to the new fixpoint) inside ONE launch, one workgroup per mesh;
 //   fc_geodesic_ball_count/fill  one workgroup per query sample: the single-source field bounded by epsilon, then the samples of
 //                                the query's mesh with d < epsilon as rows [query, position], at most K nearest of them.
-// Both rest on one relaxation loop (gf_relax).  A workgroup of 1024 threads owns one problem; thread t owns the vertices
-// t, t + 1024, ... of its range and is the only writer of their distances.  A vertex is pulled only while its dirty flag is set.
-// Flags are double-buffered: in a sweep the owner reads and clears cur[v]; a vertex whose distance drops sets nxt[u] = 1 on all
-// its neighbours; the buffers swap at the barrier.  Why the result is the least fixpoint whatever the schedule: every value ever
-// written is the rounded length of a path from a source (an upper bound of the fixpoint, fl32(a + l) being monotone in a), and
-// take the LAST pull of v, in sweep s: it left d[v] <= fl32(d_read[u] + len) for every neighbour u.  If d[u] dropped at or after
-// that read, in a sweep s' >= s, then u set nxt[v] in s' and v was pulled again in s' + 1 > s, so it was not the last pull: on
-// every edge d[v] <= fl32(d[u] + len) holds at the end, and that state is the fixpoint (header of fc_geodesic.hip).  Nothing in
-// this needs an order between a thread's accesses inside a sweep; only the barrier orders.  A flag byte is written with the
-// value it is meant to have by whoever writes it (cur: 0 by the owner; nxt: 1 by anyone), so concurrent stores agree.
-// The incremental start of a round is legitimate for the same reason: after d[new] = 0 the state is pointwise an upper bound of
-// the new fixpoint, and only the neighbours of `new` can violate their edge condition: they are the ones flagged.
-// The bounded field of a ball accepts a candidate only if it is < epsilon; a prefix of a shortest path is never longer than the
-// path (float32 additions of non-negative lengths are monotone), so it equals the unbounded field wherever that is < epsilon.
-// Loops are bounded by the problem: a relaxation runs at most n + 1 sweeps, a mesh exactly n_samples rounds.  No atomics.
+// Both rest on one relaxation loop, gf_relax of fc_geodesic_relax.hpp, whose header says why the flagged relaxation reaches the
+// least fixpoint whatever the schedule, why a round may start from the previous field, and why the field bounded by epsilon
+// equals the unbounded one below epsilon.  A mesh runs exactly n_samples rounds.  No atomics.
 #include <limits.h>
 #include "../../include/fieldconv_hip.h"
 #include "fc_common.hpp"
@@ -47,12 +35,8 @@ __global__ __launch_bounds__(kGfThreads) void geodesic_fps_kernel(const gfps_arg
     __shared__ unsigned long long s_key[kGfWaves];
     const int p = blockIdx.x, t = threadIdx.x;
     // whatever the tables hold, a mesh reads and writes inside [0,V) and its own slots of idx only
-    int v0 = 0, v1 = a.g.V;
-    if (a.pos_ptr) {
-        v0 = (int)gf_clamp(a.pos_ptr[p], 0, a.g.V);
-        v1 = (int)gf_clamp(a.pos_ptr[p + 1], v0, a.g.V);
-    }
-    const int n = v1 - v0;
+    int v0, n;
+    gf_mesh_range(a.pos_ptr, p, a.g.V, v0, n);
     if ((n <= a.lds_vertices) != kLds || n < 1) return;          // (uniform over the workgroup)
     const int64_t o0 = gf_clamp(a.out_ptr[p], 0, a.total_out);
     const int64_t rounds = gf_clamp(a.n_samples[p], 0, min((int64_t)n, a.total_out - o0));
@@ -136,39 +120,17 @@ __global__ __launch_bounds__(kGfThreads) void geodesic_ball_kernel(const gball_a
     const int t = threadIdx.x;
     const int q = a.q0 + (int)blockIdx.x;
     if (q < 0 || q >= a.S) return;
-    int v0 = 0, v1 = a.g.V, s0 = 0, s1 = a.S;
-    if (a.pos_ptr) {
-        int lo = 0, hi = a.B - 1;          // the last mesh whose sample range begins at or before q
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.smp_ptr[mid] <= q) lo = mid; else hi = mid - 1;
-        }
-        v0 = (int)gf_clamp(a.pos_ptr[lo], 0, a.g.V);
-        v1 = (int)gf_clamp(a.pos_ptr[lo + 1], v0, a.g.V);
-        s0 = (int)gf_clamp(a.smp_ptr[lo], 0, a.S);
-        s1 = (int)gf_clamp(a.smp_ptr[lo + 1], s0, a.S);
-    }
-    const int n = v1 - v0;
+    const int mesh = a.pos_ptr ? gf_mesh_of(a.smp_ptr, a.B, q) : 0;
+    int v0, n, s0, ns;
+    gf_mesh_range(a.pos_ptr, mesh, a.g.V, v0, n);
+    gf_mesh_range(a.smp_ptr, mesh, a.S, s0, ns);          // the samples of the mesh: positions [s0, s1), by the same rule
+    const int s1 = s0 + ns;
     if ((n <= a.lds_vertices) != kLds || n > a.max_range) return;          // (uniform over the workgroup)
     uint8_t* const slot = kLds ? reinterpret_cast<uint8_t*>(smem) : a.ws + a.ws_stride * blockIdx.x;
-    const int cap = kLds ? a.lds_vertices : n;
-    float* const d = reinterpret_cast<float*>(slot);
-    uint8_t* cur = slot + 4 * (size_t)cap;
-    uint8_t* nxt = cur + cap;
-    const float inf = __int_as_float(0x7f800000);
-
-    for (int i = t; i < n; i += kGfThreads) {
-        d[i] = inf;
-        cur[i] = 0, nxt[i] = 0;
-    }
-    __syncthreads();
-    const int64_t src = a.sample_idx[q] - v0;
-    if (src >= 0 && src < n) {
-        if (t == 0) d[src] = 0.f;
-        gf_flag_neighbours(a.g, v0, n, (int)src, cur, t);
-        __syncthreads();
-        gf_relax(a.g, v0, n, d, cur, nxt, a.eps, t);
-    }
+    float* d;
+    uint8_t *cur, *nxt;
+    gf_carve(slot, kLds ? a.lds_vertices : n, d, cur, nxt);
+    gf_single_source(a.g, v0, n, a.sample_idx[q] - v0, d, cur, nxt, a.eps, t);          // (a source outside the range: an empty ball)
 
     // the samples of this mesh inside the ball: d < eps (the source holds 0, every other finite value passed the bound)
     auto key_of = [&](int j, unsigned long long& key) -> bool {
@@ -224,48 +186,30 @@ __global__ __launch_bounds__(kGfThreads) void geodesic_ball_kernel(const gball_a
 
 namespace {
 
-using fc::gf_allow_lds;
 using fc::gf_graph_ok;
 
-// the LDS share of a launch: ranges up to this size go to the LDS instantiation
-int32_t gf_lds_share(int32_t max_range, bool tables) { return max_range <= fc::kGfLdsVertices ? max_range : (tables ? fc::kGfLdsVertices : 0); }
-
-size_t gf_ball_stride(int32_t max_range) { return (6 * (size_t)max_range + 15) / 16 * 16; }
-
 template <bool kFill>
-int gf_ball_launch(fc::gball_args a, int32_t nq, int32_t max_range, hipStream_t s) {
+int gf_ball_launch(const fc::gball_args& a, int32_t nq, int32_t max_range, hipStream_t s) {
     static bool lds_ok[fc::kMaxDevices] = {};          // (per instantiation of this template: per kernel)
-    a.lds_vertices = gf_lds_share(max_range, a.pos_ptr != nullptr);
-    if (a.lds_vertices > 0) {
-        const size_t lds = 6 * (size_t)a.lds_vertices;
-        if (lds > 64 * 1024) {
-            const int st = gf_allow_lds(reinterpret_cast<const void*>(&fc::geodesic_ball_kernel<true, kFill>), lds_ok, 6 * (size_t)fc::kGfLdsVertices);
-            if (st != FC_OK) return st;
-        }
-        hipLaunchKernelGGL((fc::geodesic_ball_kernel<true, kFill>), dim3((unsigned)nq), dim3(fc::kGfThreads), lds, s, a);
-    }
-    if (max_range > fc::kGfLdsVertices)
-        hipLaunchKernelGGL((fc::geodesic_ball_kernel<false, kFill>), dim3((unsigned)nq), dim3(fc::kGfThreads), 0, s, a);
-    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+    return fc::gf_launch_pair(fc::geodesic_ball_kernel<true, kFill>, fc::geodesic_ball_kernel<false, kFill>, a, (unsigned)nq, max_range,
+                              a.pos_ptr != nullptr, [](size_t n) { return 6 * n; }, 6 * (size_t)fc::kGfLdsVertices, 0, lds_ok, s);
 }
 
 bool gf_ball_args(fc::gball_args& a, const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
                   const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S, int32_t q0, int32_t nq,
                   float epsilon, int32_t K, void* workspace, size_t workspace_bytes, int* status) {
     *status = FC_ERR_BAD_ARGUMENT;
-    if (!gf_graph_ok(rowptr, nbr, length, V, E) || S < 1 || B < 1 || !sample_idx || max_range < 0 || max_range > V || K < 1 || !(epsilon > 0.f))
+    if (!gf_graph_ok(rowptr, nbr, length, V, E) || !fc::gf_batch_ok(pos_ptr, sample_ptr, B, max_range, V, S, q0, nq) || !sample_idx || K < 1 ||
+        !(epsilon > 0.f))
         return false;
-    if ((pos_ptr == nullptr) != (sample_ptr == nullptr) || (!pos_ptr && (B != 1 || max_range != V))) return false;
-    if (q0 < 0 || nq < 0 || (int64_t)q0 + nq > S) return false;
-    const size_t need = fc_geodesic_ball_workspace_bytes(max_range, nq);
-    if (need && (!workspace || workspace_bytes < need)) {
+    if (!fc::gf_workspace_ok(fc_geodesic_ball_workspace_bytes(max_range, nq), workspace, workspace_bytes)) {
         *status = FC_ERR_WORKSPACE;
         return false;
     }
     a.g = {rowptr, nbr, length, V, E};
     a.pos_ptr = pos_ptr, a.smp_ptr = sample_ptr, a.B = B;
     a.sample_idx = sample_idx, a.S = S, a.q0 = q0, a.eps = epsilon, a.K = K;
-    a.ws = static_cast<uint8_t*>(workspace), a.ws_stride = gf_ball_stride(max_range), a.max_range = max_range;
+    a.ws = static_cast<uint8_t*>(workspace), a.ws_stride = fc::gf_slot_bytes(max_range), a.max_range = max_range;
     *status = FC_OK;
     return true;
 }
@@ -287,29 +231,18 @@ int fc_geodesic_fps(const int32_t* rowptr, const int32_t* nbr, const float* leng
         total_out < 1 || !idx || !dist)
         return FC_ERR_BAD_ARGUMENT;
     if (!pos_ptr && (B != 1 || max_range != V)) return FC_ERR_BAD_ARGUMENT;
-    const size_t need = fc_geodesic_fps_workspace_bytes(V, max_range);
-    if (need && (!workspace || workspace_bytes < need)) return FC_ERR_WORKSPACE;
+    if (!fc::gf_workspace_ok(fc_geodesic_fps_workspace_bytes(V, max_range), workspace, workspace_bytes)) return FC_ERR_WORKSPACE;
     static bool lds_ok[fc::kMaxDevices] = {};
-    hipStream_t s = static_cast<hipStream_t>(stream);
     fc::gfps_args a = {};
     a.g = {rowptr, nbr, length, V, E};
     a.pos_ptr = pos_ptr, a.n_samples = n_samples, a.start = start, a.out_ptr = out_ptr, a.total_out = total_out;
     a.idx = idx, a.dist = dist, a.sweeps = sweeps, a.ws = static_cast<uint8_t*>(workspace);
-    a.lds_vertices = gf_lds_share(max_range, pos_ptr != nullptr);
-    if (a.lds_vertices > 0) {
-        const size_t lds = 7 * (size_t)a.lds_vertices;
-        if (lds > 64 * 1024) {
-            const int st = gf_allow_lds(reinterpret_cast<const void*>(&fc::geodesic_fps_kernel<true>), lds_ok, 7 * (size_t)fc::kGfLdsVertices);
-            if (st != FC_OK) return st;
-        }
-        hipLaunchKernelGGL(fc::geodesic_fps_kernel<true>, dim3((unsigned)B), dim3(fc::kGfThreads), lds, s, a);
-    }
-    if (max_range > fc::kGfLdsVertices) hipLaunchKernelGGL(fc::geodesic_fps_kernel<false>, dim3((unsigned)B), dim3(fc::kGfThreads), 0, s, a);
-    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+    return fc::gf_launch_pair(fc::geodesic_fps_kernel<true>, fc::geodesic_fps_kernel<false>, a, (unsigned)B, max_range, pos_ptr != nullptr,
+                              [](size_t n) { return 7 * n; }, 7 * (size_t)fc::kGfLdsVertices, 0, lds_ok, static_cast<hipStream_t>(stream));
 }
 
 size_t fc_geodesic_ball_workspace_bytes(int32_t max_range, int32_t queries) {
-    return max_range > fc::kGfLdsVertices && queries > 0 ? gf_ball_stride(max_range) * (size_t)queries : 0;
+    return max_range > fc::kGfLdsVertices && queries > 0 ? fc::gf_slot_bytes(max_range) * (size_t)queries : 0;
 }
 
 int fc_geodesic_ball_count(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,

@@ -2,8 +2,8 @@
 // metric of fc_geodesic.hip -- not the Vector Heat Method of the reference's fcutils:
 //   fc_vertex_frames     n_v = normalised sum of the incident faces' cross products (a fixed order over a vertex-to-face CSR),
 //                        e1 = normalize(ref x n), e2 = n x e1: every operation a float32 operation rounded on its own;
-//   fc_logmap            one workgroup per query sample s: (1) the distance field bounded by `bound` (gf_relax, the ball kernel's
-//                        loop); (2) the reached vertices are compacted into a ball, hop counts h over the tight edges
+//   fc_logmap            one workgroup per query sample s: (1) the distance field bounded by `bound` (gf_single_source, as
+//                        in the ball kernel); (2) the reached vertices are compacted into a ball, hop counts h over the tight edges
 //                        fl32(d[u] + len) == d[v] are swept to their least fixpoint and pred[v] = the lowest-numbered tight u with
 //                        h[u] = h[v] - 1; (3) the tree is unfolded level by level into s's tangent plane, X[v] = rho X[u],
 //                        L[v] = L[u] + conj(X[u]) c; (4) the query's rows [s, t] read L[t], X[t].
@@ -173,7 +173,8 @@ __device__ __forceinline__ void lm_tree(const lm_args& a, const lm_ball ball, in
         for (int i = t; i < m; i += kGfThreads) {
             const int vi = ball.vid[i];
             if (vi == src) continue;
-            const int e0 = max(a.g.rowptr[v0 + vi], 0), e1 = min(a.g.rowptr[v0 + vi + 1], a.g.E);
+            int e0, e1;
+            gf_row(a.g, v0 + vi, e0, e1);
             const float dv = ball.d[i];
             const int old = ball.h[i];
             int best = old;
@@ -196,7 +197,8 @@ __device__ __forceinline__ void lm_tree(const lm_args& a, const lm_ball ball, in
     for (int i = t; i < m; i += kGfThreads) {
         const int vi = ball.vid[i], hi = ball.h[i];
         if (vi == src || hi == INT_MAX) continue;
-        const int e0 = max(a.g.rowptr[v0 + vi], 0), e1 = min(a.g.rowptr[v0 + vi + 1], a.g.E);
+        int e0, e1;
+        gf_row(a.g, v0 + vi, e0, e1);
         const float dv = ball.d[i];
         for (int e = e0; e < e1; ++e) {
             const int j = slot_of(a.g.nbr[e] - v0);
@@ -274,17 +276,8 @@ __global__ __launch_bounds__(kGfThreads) void logmap_kernel(const lm_args a) {
     const int t = threadIdx.x;
     const int q = a.q0 + (int)blockIdx.x;
     if (q < 0 || q >= a.S) return;
-    int v0 = 0, v1 = a.g.V;
-    if (a.pos_ptr) {
-        int lo = 0, hi = a.B - 1;          // the last mesh whose sample range begins at or before q
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.smp_ptr[mid] <= q) lo = mid; else hi = mid - 1;
-        }
-        v0 = (int)gf_clamp(a.pos_ptr[lo], 0, a.g.V);
-        v1 = (int)gf_clamp(a.pos_ptr[lo + 1], v0, a.g.V);
-    }
-    const int n = v1 - v0;
+    int v0, n;
+    gf_mesh_range(a.pos_ptr, a.pos_ptr ? gf_mesh_of(a.smp_ptr, a.B, q) : 0, a.g.V, v0, n);
     if ((n <= a.lds_vertices) != kLds) return;          // (uniform over the workgroup) the other instantiation's query
     const int64_t src = a.sample_idx[q] - v0;
     if (n > a.max_range || src < 0 || src >= n) {
@@ -299,24 +292,14 @@ __global__ __launch_bounds__(kGfThreads) void logmap_kernel(const lm_args a) {
     }
     if (!a.dbg_hops && gf_clamp(a.row_ptr[q], 0, a.R) >= gf_clamp(a.row_ptr[q + 1], 0, a.R)) return;          // no rows: nothing to solve
 
-    const size_t lds_mesh = kLds ? (6 * (size_t)a.lds_vertices + 15) / 16 * 16 : 0;
+    const size_t lds_mesh = kLds ? gf_slot_bytes(a.lds_vertices) : 0;
     uint8_t* const own = a.ws + a.ws_stride * blockIdx.x;
     uint8_t* const slot = kLds ? reinterpret_cast<uint8_t*>(smem) : own;
-    const int cap = kLds ? a.lds_vertices : n;
-    float* const d = reinterpret_cast<float*>(slot);
-    uint8_t* cur = slot + 4 * (size_t)cap;
-    uint8_t* nxt = cur + cap;
+    float* d;
+    uint8_t *cur, *nxt;
+    gf_carve(slot, kLds ? a.lds_vertices : n, d, cur, nxt);
+    gf_single_source(a.g, v0, n, src, d, cur, nxt, a.bound, t);
     const float inf = __int_as_float(0x7f800000);
-
-    for (int i = t; i < n; i += kGfThreads) {
-        d[i] = inf;
-        cur[i] = 0, nxt[i] = 0;
-    }
-    __syncthreads();
-    if (t == 0) d[src] = 0.f;
-    gf_flag_neighbours(a.g, v0, n, (int)src, cur, t);
-    __syncthreads();
-    gf_relax(a.g, v0, n, d, cur, nxt, a.bound, t);
 
     int m = 0;
     for (int base = 0; base < n; base += kGfThreads) m += __syncthreads_count(base + t < n && d[base + t] < inf);
@@ -364,7 +347,7 @@ namespace {
 
 int32_t lm_even(int32_t x) { return (x + 1) & ~1; }
 
-size_t lm_mesh_bytes(int32_t max_range) { return max_range > fc::kGfLdsVertices ? (6 * (size_t)max_range + 15) / 16 * 16 : 0; }
+size_t lm_mesh_bytes(int32_t max_range) { return max_range > fc::kGfLdsVertices ? fc::gf_slot_bytes(max_range) : 0; }
 
 size_t lm_ball_bytes(int32_t max_range, int32_t ball_lds) {
     return max_range > ball_lds ? ((size_t)fc::kLmBallBytes * lm_even(max_range) + 15) / 16 * 16 : 0;
@@ -395,15 +378,13 @@ int fc_logmap(const int32_t* rowptr, const int32_t* nbr, const float* length, in
               const int64_t* sample_idx, int32_t S, int32_t q0, int32_t nq, float bound, const int64_t* row_ptr, const int64_t* row_target,
               int64_t n_rows, float* log_mag, float* log_ang, float* xp, uint8_t* reached, int32_t* debug_pred, int32_t* debug_hops,
               int32_t ball_lds, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!fc::gf_graph_ok(rowptr, nbr, length, V, E) || S < 1 || B < 1 || !sample_idx || max_range < 1 || max_range > V || !(bound > 0.f) ||
-        !pos || !normal || !e1 || !e2 || !row_ptr || n_rows < 0 || ball_lds < 0 || ball_lds > fc::kLmBallLds)
+    if (!fc::gf_graph_ok(rowptr, nbr, length, V, E) || !fc::gf_batch_ok(pos_ptr, sample_ptr, B, max_range, V, S, q0, nq) || max_range < 1 ||
+        !sample_idx || !(bound > 0.f) || !pos || !normal || !e1 || !e2 || !row_ptr || n_rows < 0 || ball_lds < 0 || ball_lds > fc::kLmBallLds ||
+        (debug_pred == nullptr) != (debug_hops == nullptr))
         return FC_ERR_BAD_ARGUMENT;
-    if ((pos_ptr == nullptr) != (sample_ptr == nullptr) || (!pos_ptr && (B != 1 || max_range != V))) return FC_ERR_BAD_ARGUMENT;
-    if (q0 < 0 || nq < 0 || (int64_t)q0 + nq > S || (debug_pred == nullptr) != (debug_hops == nullptr)) return FC_ERR_BAD_ARGUMENT;
     if (n_rows > 0 && (!row_target || !log_mag || !log_ang || !xp || !reached)) return FC_ERR_BAD_ARGUMENT;
     if (nq == 0 || (n_rows == 0 && !debug_hops)) return FC_OK;
-    const size_t need = fc_logmap_workspace_bytes(max_range, nq, ball_lds);
-    if (need && (!workspace || workspace_bytes < need)) return FC_ERR_WORKSPACE;
+    if (!fc::gf_workspace_ok(fc_logmap_workspace_bytes(max_range, nq, ball_lds), workspace, workspace_bytes)) return FC_ERR_WORKSPACE;
     fc::lm_args a = {};
     a.g = {rowptr, nbr, length, V, E};
     a.pos_ptr = pos_ptr, a.smp_ptr = sample_ptr, a.B = B;
@@ -415,21 +396,13 @@ int fc_logmap(const int32_t* rowptr, const int32_t* nbr, const float* length, in
     a.ws = static_cast<uint8_t*>(workspace);
     a.ws_ball_off = lm_mesh_bytes(max_range), a.ws_stride = a.ws_ball_off + lm_ball_bytes(max_range, ball_lds);
     a.max_range = max_range, a.ball_lds = ball_lds;
-    a.lds_vertices = max_range <= fc::kGfLdsVertices ? max_range : (pos_ptr ? fc::kGfLdsVertices : 0);
-    static bool lds_ok[fc::kMaxDevices] = {};          // (dynamic LDS above 64 KiB has to be allowed once per device)
-    const size_t most = (6 * (size_t)fc::kGfLdsVertices + 15) / 16 * 16 + (size_t)fc::kLmBallBytes * fc::kLmBallLds;
+    static bool lds_ok[fc::kMaxDevices] = {};
+    // the ball state follows the range's slot in LDS; the instantiation whose ranges relax in global memory keeps the balls there
     const size_t ball = (size_t)fc::kLmBallBytes * lm_even(ball_lds);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a.lds_vertices > 0) {
-        const size_t lds = (6 * (size_t)a.lds_vertices + 15) / 16 * 16 + ball;
-        if (lds > 64 * 1024) {
-            const int st = fc::gf_allow_lds(reinterpret_cast<const void*>(&fc::logmap_kernel<true>), lds_ok, most);
-            if (st != FC_OK) return st;
-        }
-        hipLaunchKernelGGL(fc::logmap_kernel<true>, dim3((unsigned)nq), dim3(fc::kGfThreads), lds, s, a);
-    }
-    if (max_range > fc::kGfLdsVertices) hipLaunchKernelGGL(fc::logmap_kernel<false>, dim3((unsigned)nq), dim3(fc::kGfThreads), ball, s, a);
-    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+    return fc::gf_launch_pair(fc::logmap_kernel<true>, fc::logmap_kernel<false>, a, (unsigned)nq, max_range, pos_ptr != nullptr,
+                              [=](size_t n) { return fc::gf_slot_bytes(n) + ball; },
+                              fc::gf_slot_bytes(fc::kGfLdsVertices) + (size_t)fc::kLmBallBytes * fc::kLmBallLds, ball, lds_ok,
+                              static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -16,10 +16,12 @@ import torch
 from . import _lib
 from .pooling import check_ptr, ptr_on
 
-# Vertices of one mesh whose distances and labels are solved in LDS (fc_geodesic_lds_vertices: 8 B per vertex of the CU's
-# 160 KiB); a larger mesh runs the same loop in global memory, still in one workgroup.
+# Vertices of one mesh solved in LDS by every solver of the family (fc_geodesic_lds_vertices: 8 B per vertex of the CU's 160 KiB
+# for distances and labels, 7 B for sampling, 6 B for a ball); a larger mesh runs the same loops in global memory, still one
+# workgroup per problem.
 LDS_VERTICES = 20000
 _ROW_CHUNK_FLOATS = 1 << 26          # distance rows per launch: at most 256 MiB of them
+_WORKSPACE_BYTES = 1 << 28           # queries per launch where they need workspace slots: at most 256 MiB of them
 
 
 def _ptr(t):
@@ -140,20 +142,64 @@ def _check_diagonals(graph, diagonals, what):
                          'and leave diagonals at False')
 
 
+def _mesh_on(pos, face, what):
+    """a checked mesh -> (pos, face) on the device, face's vertex numbers checked (one synchronisation), and the device"""
+    dev = _device_of(pos)
+    with torch.cuda.device(dev):
+        return pos.detach().to(dev).contiguous(), _face_on(face, int(pos.shape[0]), dev, what), dev
+
+
 def _prepare(pos, face, graph, what, diagonals=False):
-    """-> (pos, face or None, graph) on the device, and the device"""
+    """-> (pos, face or None, graph) on the device, and the device; face is None where graph was given: nothing looked at it"""
     _check_mesh(pos, face, what)
     _check_diagonals(graph, diagonals, what)
     if diagonals and 9 * face.shape[1] > 2 ** 31 - 1:
         raise ValueError(f'{what}: with diagonals a mesh has up to 9 directed edges per face, and edges are 32-bit indices in the kernels')
+    if graph is None:
+        p, f, dev = _mesh_on(pos, face, what)
+        with torch.cuda.device(dev):
+            return p, f, _edge_graph(p, f, dev, diagonals), dev
     dev = _device_of(pos)
-    V = int(pos.shape[0])
     with torch.cuda.device(dev):
-        p = pos.detach().to(dev).contiguous()
-        if graph is not None:
-            return p, None, _graph_on(graph, V, dev, what), dev
-        f = _face_on(face, V, dev, what)
-        return p, f, _edge_graph(p, f, dev, diagonals), dev
+        return pos.detach().to(dev).contiguous(), None, _graph_on(graph, int(pos.shape[0]), dev, what), dev
+
+
+def _rows_per_call(rows_per_call, V, what):
+    """the checked number of (V,) distance rows per launch; None: 256 MiB of them"""
+    if rows_per_call is None:
+        return max(1, _ROW_CHUNK_FLOATS // V)
+    if isinstance(rows_per_call, bool) or int(rows_per_call) != rows_per_call or rows_per_call < 1:
+        raise ValueError(f'{what}: rows_per_call must be an integer >= 1, got {rows_per_call!r}')
+    return int(rows_per_call)
+
+
+def _batch_tables(pos_ptr, sample_ptr, V, S, what, name, sample_idx=None):
+    """pos_ptr and the table `name` over the S samples: both None, or the (B+1,) range tables of a MeshBatch
+    -> (B, max_range, host pos_ptr, host sample_ptr, on), on(device) being both tables on that device (None, None without tables).
+    sample_idx: the samples of a mesh must be vertices of that mesh, checked on sample_idx's own device (one synchronisation)."""
+    if (pos_ptr is None) != (sample_ptr is None):
+        raise ValueError(f'{what}: pos_ptr and {name} go together (the ranges of a MeshBatch): give both or neither')
+    if pos_ptr is None:
+        return 1, V, None, None, lambda dev: (None, None)
+    host_p, host_s = check_ptr(pos_ptr, V, what, 'pos_ptr'), check_ptr(sample_ptr, S, what, name)
+    if len(host_p) != len(host_s):
+        raise ValueError(f'{what}: pos_ptr describes {len(host_p) - 1} meshes, {name} {len(host_s) - 1}')
+    B = len(host_p) - 1
+    if sample_idx is not None:
+        at = sample_idx.device
+        mesh_of = torch.searchsorted(torch.tensor(host_p, dtype=torch.int64, device=at), sample_idx.contiguous(), right=True) - 1
+        counts = torch.tensor([b - a for a, b in zip(host_s, host_s[1:])], dtype=torch.int64, device=at)
+        if bool((mesh_of != torch.repeat_interleave(torch.arange(B, device=at), counts)).any()):
+            raise ValueError(f'{what}: sample_idx of a mesh must name vertices of that mesh (rows of the union inside its pos_ptr range)')
+    return (B, max(b - a for a, b in zip(host_p, host_p[1:])), host_p, host_s,
+            lambda dev: (ptr_on(pos_ptr, host_p, dev), ptr_on(sample_ptr, host_s, dev)))
+
+
+def _query_windows(S, slot_bytes):
+    """the launches over S queries -> (queries per launch, its windows [(q0, nq), ...]): all at once where a query needs no
+    workspace slot, else as many as keep the slots under 256 MiB"""
+    per_call = max(1, min(S, _WORKSPACE_BYTES // slot_bytes)) if slot_bytes else S
+    return per_call, [(q0, min(per_call, S - q0)) for q0 in range(0, S, per_call)]
 
 
 def mesh_edge_graph(pos, face, diagonals=False):
@@ -196,11 +242,7 @@ def geodesic_distances(pos, face, sources, graph=None, rows_per_call=None, retur
     V = int(pos.shape[0])
     _check_index(sources, V, what, 'sources')
     S = int(sources.numel())
-    if rows_per_call is None:
-        rows_per_call = max(1, _ROW_CHUNK_FLOATS // V)
-    if isinstance(rows_per_call, bool) or int(rows_per_call) != rows_per_call or rows_per_call < 1:
-        raise ValueError(f'{what}: rows_per_call must be an integer >= 1, got {rows_per_call!r}')
-    rows_per_call = min(int(rows_per_call), S)
+    rows_per_call = min(_rows_per_call(rows_per_call, V, what), S)
     p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     E = int(nbr.numel())
@@ -234,29 +276,15 @@ def nearest_sample(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=N
     V = int(pos.shape[0])
     _check_index(sample_idx, V, what, 'sample_idx')
     S = int(sample_idx.numel())
-    if (pos_ptr is None) != (sample_ptr is None):
-        raise ValueError(f'{what}: pos_ptr and sample_ptr go together (the ranges of a MeshBatch): give both or neither')
-    B, max_range, host_p, host_s = 1, V, None, None
-    if pos_ptr is not None:
-        host_p, host_s = check_ptr(pos_ptr, V, what, 'pos_ptr'), check_ptr(sample_ptr, S, what, 'sample_ptr')
-        if len(host_p) != len(host_s):
-            raise ValueError(f'{what}: pos_ptr describes {len(host_p) - 1} meshes, sample_ptr {len(host_s) - 1}')
-        B = len(host_p) - 1
-        if any(b == a for a, b in zip(host_s, host_s[1:])):
-            raise ValueError(f'{what}: a mesh of the batch has no samples')
-        max_range = max(b - a for a, b in zip(host_p, host_p[1:]))
+    B, max_range, _, host_s, tables_on = _batch_tables(pos_ptr, sample_ptr, V, S, what, 'sample_ptr', sample_idx)
+    if host_s is not None and any(b == a for a, b in zip(host_s, host_s[1:])):
+        raise ValueError(f'{what}: a mesh of the batch has no samples')
     p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     E = int(nbr.numel())
     with torch.cuda.device(dev):
         src = sample_idx.detach().to(dev).contiguous()
-        pp = sp = None
-        if pos_ptr is not None:
-            pp, sp = ptr_on(pos_ptr, host_p, dev), ptr_on(sample_ptr, host_s, dev)
-            mesh_of = torch.searchsorted(pp, src, right=True) - 1
-            want = torch.repeat_interleave(torch.arange(B, device=dev), sp[1:] - sp[:-1])
-            if bool((mesh_of != want).any()):
-                raise ValueError(f'{what}: sample_idx of a mesh must name vertices of that mesh (rows of the union inside its pos_ptr range)')
+        pp, sp = tables_on(dev)
         nbytes = lib.fc_geodesic_workspace_bytes(V, max_range)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
         dist = torch.empty(V, dtype=torch.float32, device=dev)
@@ -321,10 +349,8 @@ def vertex_masses(pos, face):
     the order (corner 0 of every face, corner 1, corner 2; faces ascending) -- a fixed order, the same bits on every run."""
     what = 'vertex_masses'
     _check_mesh(pos, face, what)
-    dev = _device_of(pos)
+    p, f, dev = _mesh_on(pos, face, what)
     with torch.cuda.device(dev):
-        p = pos.detach().to(dev).contiguous()
-        f = _face_on(face, int(pos.shape[0]), dev, what)
         return _segment_sum(_face_areas(p, f, dev).repeat(3), f.reshape(-1), int(p.shape[0]), 3.0, dev).to(pos.device)
 
 
@@ -346,10 +372,9 @@ def surface_area(pos, face):
     """The mesh's area as a Python float: the float32 triangle areas added in float64."""
     what = 'surface_area'
     _check_mesh(pos, face, what)
-    dev = _device_of(pos)
+    p, f, dev = _mesh_on(pos, face, what)
     with torch.cuda.device(dev):
-        p = pos.detach().to(dev).contiguous()
-        return float(_face_areas(p, _face_on(face, int(pos.shape[0]), dev, what), dev).to(torch.float64).sum())
+        return float(_face_areas(p, f, dev).to(torch.float64).sum())
 
 
 def geodesic_error(pos, face, pred, target, normalize=True, graph=None, rows_per_call=None, diagonals=False):
@@ -374,13 +399,11 @@ def geodesic_error(pos, face, pred, target, normalize=True, graph=None, rows_per
         uniq, inv = torch.unique(target.to(dev), return_inverse=True)
         pr = pred.to(dev)
         U = int(uniq.numel())
-        step = max(1, _ROW_CHUNK_FLOATS // V) if rows_per_call is None else rows_per_call
-        if isinstance(step, bool) or int(step) != step or step < 1:
-            raise ValueError(f'{what}: rows_per_call must be an integer >= 1, got {rows_per_call!r}')
+        step = _rows_per_call(rows_per_call, V, what)
         p = pos.detach().to(dev)
         err = torch.empty(int(pr.numel()), dtype=torch.float32, device=dev)
-        for u0 in range(0, U, int(step)):
-            u1 = min(U, u0 + int(step))
+        for u0 in range(0, U, step):
+            u1 = min(U, u0 + step)
             rows = geodesic_distances(p, face, uniq[u0:u1], graph=graph)
             mine = torch.nonzero((inv >= u0) & (inv < u1))[:, 0]
             err[mine] = rows[inv[mine] - u0, pr[mine]]

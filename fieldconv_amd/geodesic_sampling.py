@@ -12,13 +12,9 @@ ValueError before anything is launched.  Nothing here is differentiable."""
 import torch
 
 from . import _lib
-from .geodesic import _check_diagonals, _check_index, _check_mesh, _prepare, _ptr, _stream
+from .geodesic import LDS_VERTICES          # noqa: F401  (the family's one LDS capacity, readable from here as well)
+from .geodesic import _batch_tables, _check_diagonals, _check_index, _check_mesh, _prepare, _ptr, _query_windows, _stream
 from .pooling import check_ptr, ptr_on
-
-# Vertices of one mesh solved in LDS (fc_geodesic_fps_lds_vertices: 7 B per vertex for sampling, 6 B for a ball); a larger
-# mesh runs the same loops in global memory, still one workgroup per problem.
-LDS_VERTICES = 20000
-_BALL_WORKSPACE_BYTES = 1 << 28          # queries per launch on meshes above the LDS capacity: at most 256 MiB of slots
 
 
 def _int_in(value, lo, hi, what, name, where=''):
@@ -100,8 +96,6 @@ def geodesic_farthest_point_sample_batched(pos, face, pos_ptr, n_samples, start=
     _check_diagonals(graph, diagonals, what)
     host = check_ptr(pos_ptr, int(pos.shape[0]), what, 'pos_ptr')
     B = len(host) - 1
-    if B < 1:
-        raise ValueError(f'{what}: pos_ptr describes no mesh')
     S, st = _per_mesh(n_samples, B, what, 'n_samples'), _per_mesh(start, B, what, 'start')
     for b in range(B):
         n_b = host[b + 1] - host[b]
@@ -145,45 +139,28 @@ def geodesic_radius_edges(pos, face, sample_idx, epsilon, max_num_neighbors=512,
     K = _check_k(max_num_neighbors, what)
     if K > 2 ** 31 - 1:
         raise ValueError(f'{what}: max_num_neighbors must stay below 2^31')
-    if (pos_ptr is None) != (sample_ptr is None):
-        raise ValueError(f'{what}: pos_ptr and sample_ptr go together (the ranges of a MeshBatch): give both or neither')
-    B, max_range, host_p, host_s = 1, V, None, None
-    if pos_ptr is not None:
-        host_p, host_s = check_ptr(pos_ptr, V, what, 'pos_ptr'), check_ptr(sample_ptr, S, what, 'sample_ptr')
-        if len(host_p) != len(host_s):
-            raise ValueError(f'{what}: pos_ptr describes {len(host_p) - 1} meshes, sample_ptr {len(host_s) - 1}')
-        B = len(host_p) - 1
-        max_range = max(b - a for a, b in zip(host_p, host_p[1:]))
-        at = sample_idx.device
-        mesh_of = torch.searchsorted(torch.tensor(host_p, dtype=torch.int64, device=at), sample_idx.contiguous(), right=True) - 1
-        counts = torch.tensor([b - a for a, b in zip(host_s, host_s[1:])], dtype=torch.int64, device=at)
-        if bool((mesh_of != torch.repeat_interleave(torch.arange(B, device=at), counts)).any()):
-            raise ValueError(f'{what}: sample_idx of a mesh must name vertices of that mesh (rows of the union inside its pos_ptr range)')
+    B, max_range, _, _, tables_on = _batch_tables(pos_ptr, sample_ptr, V, S, what, 'sample_ptr', sample_idx)
     p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     E_graph = int(nbr.numel())
-    per_call = S
-    if max_range > LDS_VERTICES:
-        per_call = max(1, min(S, _BALL_WORKSPACE_BYTES // lib.fc_geodesic_ball_workspace_bytes(max_range, 1)))
+    per_call, windows = _query_windows(S, lib.fc_geodesic_ball_workspace_bytes(max_range, 1))          # (no slots up to LDS_VERTICES)
     with torch.cuda.device(dev):
         src = sample_idx.detach().to(dev).contiguous()
-        pp = sp = None
-        if pos_ptr is not None:
-            pp, sp = ptr_on(pos_ptr, host_p, dev), ptr_on(sample_ptr, host_s, dev)
+        pp, sp = tables_on(dev)
         nbytes = lib.fc_geodesic_ball_workspace_bytes(max_range, per_call)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
         count = torch.empty(S, dtype=torch.int32, device=dev)
-        for q0 in range(0, S, per_call):
+        for q0, nq in windows:
             _lib.check(lib.fc_geodesic_ball_count(_ptr(ptr), _ptr(nbr), _ptr(length), V, E_graph, _ptr(pp), _ptr(sp), B, max_range, _ptr(src),
-                                                  S, q0, min(per_call, S - q0), eps, K, _ptr(count), _ptr(ws), nbytes, _stream()),
+                                                  S, q0, nq, eps, K, _ptr(count), _ptr(ws), nbytes, _stream()),
                        'fc_geodesic_ball_count')
         off = torch.zeros(S + 1, dtype=torch.int64, device=dev)
         off[1:] = torch.cumsum(count, 0, dtype=torch.int64)
         E = int(off[-1])          # the one synchronisation: E sizes the output
         edges = torch.empty((E, 2), dtype=torch.int64, device=dev)
         dist = torch.empty(E, dtype=torch.float32, device=dev) if return_dist else None
-        for q0 in range(0, S, per_call):
+        for q0, nq in windows:
             _lib.check(lib.fc_geodesic_ball_fill(_ptr(ptr), _ptr(nbr), _ptr(length), V, E_graph, _ptr(pp), _ptr(sp), B, max_range, _ptr(src),
-                                                 S, q0, min(per_call, S - q0), eps, K, _ptr(off), E, _ptr(edges), _ptr(dist), _ptr(ws),
+                                                 S, q0, nq, eps, K, _ptr(off), E, _ptr(edges), _ptr(dist), _ptr(ws),
                                                  nbytes, _stream()), 'fc_geodesic_ball_fill')
     return (edges.to(pos.device), dist.to(pos.device)) if return_dist else edges.to(pos.device)

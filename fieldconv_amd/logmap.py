@@ -18,13 +18,11 @@ import math
 import torch
 
 from . import _lib
-from .geodesic import _check_diagonals, _check_index, _check_mesh, _device_of, _face_on, _prepare, _ptr, _stream
-from .pooling import check_ptr, ptr_on
+from .geodesic import _batch_tables, _check_diagonals, _check_index, _check_mesh, _face_on, _mesh_on, _prepare, _ptr, _query_windows, _stream
 
 # Reached vertices of one query whose tree state stays in LDS (fc_logmap_ball_lds_vertices: 36 B each, beside the 6 B per
 # vertex of the mesh's relaxation state); a larger ball keeps it in a workspace slot, with the same result.
 BALL_LDS_VERTICES = 1024
-_WORKSPACE_BYTES = 1 << 28          # queries per launch where slots are needed: at most 256 MiB of them
 _TREE_ENTRIES = 1 << 24             # return_tree: at most this many (query, vertex) pairs
 
 
@@ -50,10 +48,8 @@ def vertex_frames(pos, face):
     fieldconv_amd.data.synthetic."""
     what = 'vertex_frames'
     _check_mesh(pos, face, what)
-    dev = _device_of(pos)
+    p, f, dev = _mesh_on(pos, face, what)
     with torch.cuda.device(dev):
-        p = pos.detach().to(dev).contiguous()
-        f = _face_on(face, int(pos.shape[0]), dev, what)
         return tuple(t.to(pos.device) for t in _frames(p, f, dev))
 
 
@@ -113,42 +109,22 @@ def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_
     cap = int(cap)
     if return_tree and S * V > _TREE_ENTRIES:
         raise ValueError(f'{what}: return_tree is for small cases, at most {_TREE_ENTRIES} (query, vertex) pairs, got {S} x {V}')
-    if (pos_ptr is None) != (ptr is None):
-        raise ValueError(f'{what}: pos_ptr and ptr go together (the ranges of a MeshBatch): give both or neither')
-    B, max_range, host_p, host_s = 1, V, None, None
-    if pos_ptr is not None:
-        host_p, host_s = check_ptr(pos_ptr, V, what, 'pos_ptr'), check_ptr(ptr, S, what, 'ptr')
-        if len(host_p) != len(host_s):
-            raise ValueError(f'{what}: pos_ptr describes {len(host_p) - 1} meshes, ptr {len(host_s) - 1}')
-        B = len(host_p) - 1
-        if B < 1:
-            raise ValueError(f'{what}: pos_ptr describes no mesh')
-        max_range = max(b - a for a, b in zip(host_p, host_p[1:]))
-        at = sample_idx.device
-        mesh_of = torch.searchsorted(torch.tensor(host_p, dtype=torch.int64, device=at), sample_idx.contiguous(), right=True) - 1
-        counts = torch.tensor([b - a for a, b in zip(host_s, host_s[1:])], dtype=torch.int64, device=at)
-        if bool((mesh_of != torch.repeat_interleave(torch.arange(B, device=at), counts)).any()):
-            raise ValueError(f'{what}: sample_idx of a mesh must name vertices of that mesh (rows of the union inside its pos_ptr range)')
-    p, _, (gptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
+    B, max_range, _, _, tables_on = _batch_tables(pos_ptr, ptr, V, S, what, 'ptr', sample_idx)
+    p, f, (gptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     if lib.fc_logmap_ball_lds_vertices() != BALL_LDS_VERTICES:
         raise _lib.FieldConvNativeError(f'{what}: the library keeps {lib.fc_logmap_ball_lds_vertices()} ball vertices in LDS, this module '
                                         f'says {BALL_LDS_VERTICES}: they were built from different sources')
     E_graph = int(nbr.numel())
-    per_call = S
-    slot = lib.fc_logmap_workspace_bytes(max_range, 1, cap)
-    if slot:
-        per_call = max(1, min(S, _WORKSPACE_BYTES // slot))
+    per_call, windows = _query_windows(S, lib.fc_logmap_workspace_bytes(max_range, 1, cap))
     with torch.cuda.device(dev):
-        nrm, e1, e2 = _frames(p, _face_on(face, V, dev, what), dev)
+        nrm, e1, e2 = _frames(p, _face_on(face, V, dev, what) if f is None else f, dev)          # (f is None: graph= was given)
         src = sample_idx.detach().to(dev).contiguous()
         rows = supp_edges.detach().to(dev)
         order = torch.sort(rows[:, 0], stable=True)          # the rows grouped by query
         row_ptr = torch.searchsorted(order.values.contiguous(), torch.arange(S + 1, device=dev))
         target = rows[order.indices, 1].contiguous()
-        pp = sp = None
-        if pos_ptr is not None:
-            pp, sp = ptr_on(pos_ptr, host_p, dev), ptr_on(ptr, host_s, dev)
+        pp, sp = tables_on(dev)
         nbytes = lib.fc_logmap_workspace_bytes(max_range, per_call, cap)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
         mag = torch.empty(R, dtype=torch.float32, device=dev)
@@ -159,9 +135,9 @@ def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_
         if return_tree:
             pred = torch.full((S, V), -1, dtype=torch.int32, device=dev)
             hops = torch.full((S, V), -1, dtype=torch.int32, device=dev)
-        for q0 in range(0, S, per_call):
+        for q0, nq in windows:
             _lib.check(lib.fc_logmap(_ptr(gptr), _ptr(nbr), _ptr(length), V, E_graph, _ptr(pp), _ptr(sp), B, max_range, _ptr(p), _ptr(nrm),
-                                     _ptr(e1), _ptr(e2), _ptr(src), S, q0, min(per_call, S - q0), bound, _ptr(row_ptr), _ptr(target), R,
+                                     _ptr(e1), _ptr(e2), _ptr(src), S, q0, nq, bound, _ptr(row_ptr), _ptr(target), R,
                                      _ptr(mag), _ptr(ang), _ptr(xp), _ptr(reached), _ptr(pred), _ptr(hops), cap, _ptr(ws), nbytes,
                                      _stream()), 'fc_logmap')
         back = torch.empty_like(order.indices)

@@ -16,9 +16,9 @@ weight and phase are geometry: they never receive a gradient."""
 import torch
 
 from . import _lib
-from .geodesic import _check_diagonals, _check_index, _check_mesh, _device_of, _ptr, _segment_sum, _stream, mesh_edge_graph, nearest_sample
+from .geodesic import (_batch_tables, _check_diagonals, _check_index, _check_mesh, _device_of, _ptr, _segment_sum, _stream, mesh_edge_graph,
+                       nearest_sample)
 from .logmap import _check_bound, log_map_transport
-from .pooling import check_ptr
 
 _DTYPES = {torch.float32: (0, 0), torch.float64: (1, 0), torch.complex64: (0, 1), torch.complex128: (1, 1)}          # (fc_dtype, is_complex)
 _REAL = (torch.float32, torch.float64)
@@ -201,9 +201,8 @@ def _check_batch(pos_ptr, ptr, coarse_ptr, V, S, host_c, what):
         raise ValueError(f'{what}: pos_ptr, ptr and coarse_ptr go together (the ranges of a MeshBatch and of its coarse level): give all or none')
     if not any(given):
         return None, None, None
-    hp, hs, hc = check_ptr(pos_ptr, V, what, 'pos_ptr'), check_ptr(ptr, S, what, 'ptr'), check_ptr(coarse_ptr, len(host_c), what, 'coarse_ptr')
-    if not len(hp) == len(hs) == len(hc):
-        raise ValueError(f'{what}: pos_ptr, ptr and coarse_ptr describe {len(hp) - 1}, {len(hs) - 1} and {len(hc) - 1} meshes')
+    _, _, hp, hs, _ = _batch_tables(pos_ptr, ptr, V, S, what, 'ptr')
+    hc = _batch_tables(pos_ptr, coarse_ptr, V, len(host_c), what, 'coarse_ptr')[3]
     for b in range(len(hp) - 1):
         mine = host_c[hc[b]:hc[b + 1]]
         if not mine:

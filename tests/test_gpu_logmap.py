@@ -225,6 +225,35 @@ def test_batch_equals_single_calls_and_rows_keep_their_order(dev):
     assert all(not x.is_cuda and torch.equal(bits(x), bits(y).cpu()) for x, y in zip(cpu, device_result('grid')))
 
 
+@pytest.mark.parametrize('ball_lds', [None, 0])
+def test_batch_of_a_mesh_above_the_lds_capacity_and_one_below_equals_single_calls(dev, ball_lds):
+    """one call, both instantiations: the 35-vertex lattice relaxes in LDS, the 20 001-vertex strip in global memory, and each takes
+    the other's queries for not its own; with ball_lds_vertices = 0 the global instantiation asks for no dynamic LDS at all"""
+    from fieldconv_amd.logmap import log_map_transport
+    small, strip = gref.lattice(7, 5), case('strip')
+    small_samples = np.array([0, 3, 17, 18, 34], dtype=np.int64)
+    small_edges, bound = lref.all_pairs(len(small_samples)), strip.bound
+    n, s = small[0].shape[0], len(small_samples)
+    pos, face, pos_ptr = gref.union([small, (strip.pos, strip.face)])
+    ptr = np.array([0, s, s + len(strip.sample_idx)], dtype=np.int64)
+    assert pos_ptr[1] == n == 35 and pos_ptr[2] - pos_ptr[1] == 20001 and len(strip.sample_idx) <= 8
+    got = log_map_transport(T(pos, dev), T(face, dev), T(np.concatenate((small_samples, strip.sample_idx + n)), dev),
+                            T(np.concatenate((small_edges, strip.edges + s)), dev), bound, pos_ptr=T(pos_ptr, dev), ptr=T(ptr, dev),
+                            return_reached=True, return_tree=True, ball_lds_vertices=ball_lds)
+    a = log_map_transport(T(small[0], dev), T(small[1], dev), T(small_samples, dev), T(small_edges, dev), bound, return_reached=True,
+                          return_tree=True)
+    b = device_result('strip', tree=True)
+    assert bool(a[3].any()) and not bool(a[3].all()) and bool(b[3].any())          # balls stay small: some rows in reach, some not
+    for x, y, z in zip(got[:4], a, b):
+        assert torch.equal(bits(x), bits(torch.cat((y, z))))
+    # the tree: a query's row holds -1 outside its own mesh, and predecessors are vertex numbers of the union
+    for k, (x, y, z) in enumerate(zip(got[4:], a[4:], b[4:])):
+        off = n if k == 0 else 0
+        assert tuple(x.shape) == (s + len(strip.sample_idx), n + 20001)
+        assert torch.equal(x[:s, :n], y) and torch.equal(x[s:, n:], torch.where(z >= 0, z + off, z))
+        assert bool((x[:s, n:] == -1).all()) and bool((x[s:, :n] == -1).all())
+
+
 # ------------------------------------------------------------------ 8. determinism
 def test_two_runs_give_the_same_bits(dev):
     from fieldconv_amd.logmap import log_map_transport
