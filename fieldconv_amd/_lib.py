@@ -231,6 +231,9 @@ SIGNATURES = {
     'fc_mesh_diagonals': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp, _c_int32, _vp, _vp, _vp, _vp]),
     'fc_mesh_graph_merge': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp, _vp, _vp, _vp]),
     'fc_transfer': (ctypes.c_int, [_vp] * 5 + [_c_int32] * 7 + [_vp, _vp]),
+    'fc_tangent_norm_workspace_bytes': (_sz, [_c_int32] * 4),
+    'fc_tangent_norm_forward': (ctypes.c_int, [_vp] * 4 + [_c_int32] * 4 + [ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
+    'fc_tangent_norm_backward': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 4 + [_vp, _vp, _vp, _sz, _vp]),
 }
 
 _LIB = None

@@ -22,15 +22,9 @@
 // (and to the previous bound) where they are used, so a malformed ptr gives meaningless sums but touches nothing outside
 // the buffers.
 #include "../../include/fieldconv_hip.h"
-#include "fc_common.hpp"
+#include "fc_segment.hpp"
 
 namespace fc {
-
-constexpr int kSegRows = 64;           // rows per chunk
-constexpr int kSegWaves = 4;           // wavefronts per workgroup: row (partial) / chunk (finish) phases
-constexpr int kSegThreads = 64 * kSegWaves;
-
-template <typename T> struct alignas(2 * sizeof(T)) SegCx { T x, y; };
 
 __device__ __forceinline__ float seg_sqrt(float v) { return sqrtf(v); }
 __device__ __forceinline__ double seg_sqrt(double v) { return sqrt(v); }
@@ -50,44 +44,19 @@ template <typename T, bool ABS> __device__ __forceinline__ T seg_value(const voi
     }
 }
 
-__device__ __forceinline__ int seg_bound(const int64_t* __restrict__ ptr, int b, int N) {
-    const int64_t v = ptr[b];
-    return (int)(v < 0 ? 0 : (v > N ? N : v));
-}
-
-// rows [p0, p1) of mesh b
-__device__ __forceinline__ void seg_range(const int64_t* __restrict__ ptr, int b, int N, int& p0, int& p1) {
-    p0 = seg_bound(ptr, b, N);
-    p1 = max(seg_bound(ptr, b + 1, N), p0);
-}
-
-// (a_0 + a_1) + (a_2 + a_3) over the four wavefronts' values of this lane; the result is valid in wavefront 0
-template <typename T> __device__ __forceinline__ T seg_combine(T (*acc)[64], T s, int wave, int lane) {
-    acc[wave][lane] = s;
-    __syncthreads();
-    return (acc[0][lane] + acc[1][lane]) + (acc[2][lane] + acc[3][lane]);
-}
-
 template <typename T, bool ABS>
 __global__ __launch_bounds__(kSegThreads) void segment_partial_kernel(const void* __restrict__ x, const int64_t* __restrict__ ptr, int B,
                                                                       int N, int C, T* __restrict__ partial) {
     __shared__ T acc[kSegWaves][64];
     const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
-    int lo = 0, hi = B - 1;                                  // the largest b with base(b) <= g
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (seg_bound(ptr, mid, N) / kSegRows + mid <= g) lo = mid;
-        else hi = mid - 1;
-    }
-    int p0, p1;
-    seg_range(ptr, lo, N, p0, p1);
-    const long long r0 = (long long)p0 + (long long)(g - (p0 / kSegRows + lo)) * kSegRows;
-    if (r0 < p0 || r0 >= p1) return;                         // a spare slot (the whole workgroup leaves)
-    const int r1 = (int)min(r0 + (long long)kSegRows, (long long)p1);
+    const int b = seg_mesh_of_slot(ptr, B, N, g);
+    int p0, p1, r0, r1;
+    seg_range(ptr, b, N, p0, p1);
+    if (!seg_chunk_rows(g, b, p0, p1, r0, r1)) return;       // a spare slot (the whole workgroup leaves)
     T s = (T)0;
     if (c < C)
-        for (int r = (int)r0 + wave; r < r1; r += kSegWaves) s += seg_value<T, ABS>(x, (size_t)r * C + c);
+        for (int r = r0 + wave; r < r1; r += kSegWaves) s += seg_value<T, ABS>(x, (size_t)r * C + c);
     s = seg_combine(acc, s, wave, lane);
     if (wave == 0 && c < C) partial[(size_t)g * C + c] = s;
 }
@@ -120,13 +89,7 @@ __global__ __launch_bounds__(kSegThreads) void segment_backward_kernel(const voi
     bool have = false;
     for (int r = blockIdx.x * kSegRows + wave; r < rend; r += kSegWaves) {
         if (!have || r >= p1) {                              // rows ascend: look the mesh up again only past the current one's end
-            int lo = 0, hi = B - 1;                          // the largest b with ptr[b] <= r
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (seg_bound(ptr, mid, N) <= r) lo = mid;
-                else hi = mid - 1;
-            }
-            b = lo;
+            b = seg_mesh_of_row(ptr, B, N, r);
             seg_range(ptr, b, N, p0, p1);
             have = true;
         }
@@ -158,15 +121,12 @@ __global__ __launch_bounds__(kSegThreads) void segment_backward_kernel(const voi
 
 namespace {
 
-size_t seg_round256(size_t b) { return (b + 255) / 256 * 256; }
+using fc::seg_round256;
+using fc::seg_slots;
 
 bool seg_dims_ok(int32_t N, int32_t B, int32_t C, int32_t dtype, int32_t reduce) {
-    // the channel tiles are the grid's y extent; N + 64 B stays within 32 bits so that no slot or row index overflows
-    return N >= 0 && B >= 1 && C >= 1 && C <= 64 * 65535 && (dtype == FC_F32 || dtype == FC_F64) && (reduce == 0 || reduce == 1) &&
-           (int64_t)N + 64 * (int64_t)B < 2147483647LL;
+    return fc::seg_shape_ok(N, B, C) && (dtype == FC_F32 || dtype == FC_F64) && (reduce == 0 || reduce == 1);
 }
-
-int64_t seg_slots(int32_t N, int32_t B) { return (int64_t)N / fc::kSegRows + B; }
 
 template <typename T, bool ABS>
 int seg_forward(const void* x, const int64_t* ptr, int32_t N, int32_t B, int32_t C, int32_t reduce, void* out, void* workspace,

@@ -14,7 +14,8 @@ from .mesh_pool import MeshPool
 from .linear_cross_entropy import LinearCrossEntropy
 from ..head import vertex_accuracy
 from .tangent_pool import TangentPool, TangentUnpool
+from .tangent_norm import TangentNorm
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
            'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval',
-           'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'MeshPool']
+           'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'TangentNorm', 'MeshPool']

@@ -884,6 +884,31 @@ int fc_mesh_graph_merge(const int64_t* key, const float* length, int32_t N, int3
 int fc_transfer(const void* x, const int32_t* rowptr, const int32_t* col, const void* weight, const void* phase, int32_t conj_phase,
                 int32_t n_out, int32_t n_in, int32_t n_slots, int32_t C, int32_t dtype, int32_t is_complex, void* y, void* stream);
 
+/* ---- TangentNorm: per-mesh normalisation of tangent features (csrc/fc_norm.hip) ------------------------------------------------ *
+ * x (N,C) complex (interleaved re, im of dtype: 0 = float32, 1 = float64), row-major, contiguous, device memory; mesh b owns the
+ * rows ptr[b] .. ptr[b+1] - 1 (ptr as in the per-mesh pooling section: B+1 int64 in DEVICE memory, checked by the CALLER, clamped
+ * to [0, N] by the kernels).  w (N) real of that dtype, non-negative, or NULL for 1; gain (C) real or NULL for 1; eps >= 0.
+ *   W[b] = sum_n w[n]      m[b,c] = sum_n w[n] |x[n,c]|^2 / W[b]  (0 where W[b] == 0, and for an empty mesh)
+ *   r[b,c] = 1 / sqrt(m[b,c] + eps)                     y[n,c] = gain[c] r[b,c] x[n,c]
+ * forward   writes y (N,C) complex and r (B,C) real; r is what backward takes: the statistic is not recomputed.
+ * backward  with t[b,c] = sum_n re(x) re(gy) + im(x) im(gy):
+ *             gx[n,c]  = gain[c] r[b,c] gy[n,c] - gain[c] r[b,c]^3 t[b,c] (w[n] / W[b]) x[n,c]   (second term 0 where W[b] == 0)
+ *             ggain[c] = sum_b r[b,c] t[b,c], b ascending
+ *           gx (N,C) complex or NULL, ggain (C) real or NULL, not both NULL: what is NULL is not computed.
+ * No mean is subtracted (a mean over samples would mix their frames), so only magnitudes are touched; magnitudes whose squares
+ * leave the dtype's range are outside the contract.  Sums (W, m, t) run in the input's precision in the order of the per-mesh
+ * pooling section -- 64-row chunks counted from the mesh's first row, four running sums per chunk and per mesh combined as
+ * (a_0 + a_1) + (a_2 + a_3) -- which depends on the mesh's own row count and C only: no atomics, the same bits on every run and
+ * for a mesh alone or inside a batch.  Three launches forward, at most four backward.  N >= 0, B >= 1, 1 <= C <= 64 * 65535,
+ * N + 64 B < 2^31, else FC_ERR_BAD_ARGUMENT.  Workspace (both passes): the query below; FC_ERR_WORKSPACE when it is missing or
+ * smaller.  No allocation or synchronisation inside. */
+size_t fc_tangent_norm_workspace_bytes(int32_t N, int32_t B, int32_t C, int32_t dtype);
+int fc_tangent_norm_forward(const void* x, const void* w, const int64_t* ptr, const void* gain, int32_t N, int32_t B, int32_t C, int32_t dtype,
+                            double eps, void* y, void* r, void* workspace, size_t workspace_bytes, void* stream);
+int fc_tangent_norm_backward(const void* x, const void* w, const int64_t* ptr, const void* gain, const void* r, const void* gy, int32_t N,
+                             int32_t B, int32_t C, int32_t dtype, void* gx, void* ggain, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
