@@ -10,21 +10,10 @@
 // reference's ~1k-vertex meshes (a new one every step, so a captured HIP graph does not apply) cost more than the GPU work.
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
-static size_t blk_align(size_t v) { return (v + 255) / 256 * 256; }
-
-struct Carver {             // hands out 256-byte aligned pieces of one caller-owned buffer
-    char* base;
-    size_t used = 0;
-    explicit Carver(void* p) : base(static_cast<char*>(p)) {}
-    float* take(size_t bytes) {
-        float* r = reinterpret_cast<float*>(base + used);
-        used += blk_align(bytes);
-        return r;
-    }
-};
 
 static bool mesh_valid(const fc_mesh* m, bool need_records) {
     if (!m || m->N <= 0 || m->E < 0 || m->R <= 0 || m->B < 0 || m->kind < 0 || m->kind > 2) return false;
@@ -38,10 +27,8 @@ static fc_dims conv_dims(const fc_mesh* m, int I, int O) { return fc_dims{m->N, 
 // ---- FCResNetBlock ----------------------------------------------------------------------------------------------------------
 struct ResnetPlan {
     fc_dims d1, d2;
-    int records;
-    size_t pre1, act1, pre2, wpk_b1, wpk_b2, saved;                    // bytes (aligned) of the pieces of `saved`
-    size_t wpk_f1, wpk_f2, res_out, fwd_ws, ws_fwd;                    // forward workspace
-    size_t g_pre2, g_h, g_pre1, part1, part2, gw, lin_ws, conv_ws, ws_bwd;      // backward workspace
+    int records, kind, C_in, C_mid, C_out;
+    size_t N;
 };
 
 static bool resnet_plan(const fc_mesh* m, const fc_resnet_block_params* p, ResnetPlan& pl) {
@@ -50,30 +37,44 @@ static bool resnet_plan(const fc_mesh* m, const fc_resnet_block_params* p, Resne
     pl.d2 = conv_dims(m, p->C_mid, p->C_out);
     if (!fc_supported(&pl.d1) || !fc_supported(&pl.d2)) return false;
     pl.records = m->kind != 0 ? 1 : 0;
-    const size_t N = (size_t)m->N;
-    pl.pre1 = blk_align(N * p->C_mid * 8);
-    pl.act1 = pl.pre1;
-    pl.pre2 = blk_align(N * p->C_out * 8);
-    pl.wpk_b1 = blk_align(packed_filter_floats_bwd(&pl.d1, pl.records) * sizeof(float));
-    pl.wpk_b2 = blk_align(packed_filter_floats_bwd(&pl.d2, pl.records) * sizeof(float));
-    pl.saved = pl.pre1 + pl.act1 + pl.pre2 + pl.wpk_b1 + pl.wpk_b2;
-    pl.wpk_f1 = blk_align(packed_filter_floats_fwd(&pl.d1, pl.records) * sizeof(float));
-    pl.wpk_f2 = blk_align(packed_filter_floats_fwd(&pl.d2, pl.records) * sizeof(float));
-    pl.res_out = blk_align(N * p->C_out * 8);
-    const size_t f1 = pl.records ? forward_workspace_bytes(&pl.d1, m->kind) : 0, f2 = pl.records ? forward_workspace_bytes(&pl.d2, m->kind) : 0;
-    pl.fwd_ws = blk_align(f1 > f2 ? f1 : f2);
-    pl.ws_fwd = pl.wpk_f1 + pl.wpk_f2 + pl.res_out + pl.fwd_ws;
-    pl.g_pre2 = blk_align(N * p->C_out * 8);
-    pl.g_h = blk_align(N * p->C_mid * 8);
-    pl.g_pre1 = pl.g_h;
-    pl.part1 = blk_align(fc_tangent_nonlin_backward_workspace_bytes(m->N, p->C_mid));
-    pl.part2 = blk_align(fc_tangent_nonlin_backward_workspace_bytes(m->N, p->C_out));
-    pl.gw = 0;           // (the convolutions' gW_eff tensors are not wanted: fc_backward_all pulls the partial sums back to the parameters)
-    pl.lin_ws = blk_align(fc_tangent_lin_backward_workspace_bytes(m->N, p->C_in, p->C_out));
-    const size_t b1 = backward_workspace_bytes(&pl.d1), b2 = backward_workspace_bytes(&pl.d2);
-    pl.conv_ws = blk_align(b1 > b2 ? b1 : b2);
-    pl.ws_bwd = pl.g_pre2 + pl.g_h + pl.g_pre1 + pl.part1 + pl.part2 + pl.gw + pl.lin_ws + pl.conv_ws;
+    pl.kind = m->kind;
+    pl.C_in = p->C_in, pl.C_mid = p->C_mid, pl.C_out = p->C_out;
+    pl.N = (size_t)m->N;
     return true;
+}
+
+struct ResnetSaved { float *pre1, *act1, *pre2, *wpk_b1, *wpk_b2; };
+static ResnetSaved resnet_saved(Carver& c, const ResnetPlan& pl) {
+    return {c.take<float>(pl.N * pl.C_mid * 8), c.take<float>(pl.N * pl.C_mid * 8), c.take<float>(pl.N * pl.C_out * 8),
+            c.take<float>(packed_filter_floats_bwd(&pl.d1, pl.records) * sizeof(float)),
+            c.take<float>(packed_filter_floats_bwd(&pl.d2, pl.records) * sizeof(float))};
+}
+
+struct ResnetFwdWs { float *wpk_f1, *wpk_f2, *res_out; void* conv; size_t conv_bytes; };
+static ResnetFwdWs resnet_fwd_ws(Carver& c, const ResnetPlan& pl) {
+    ResnetFwdWs w;
+    w.wpk_f1 = c.take<float>(packed_filter_floats_fwd(&pl.d1, pl.records) * sizeof(float));
+    w.wpk_f2 = c.take<float>(packed_filter_floats_fwd(&pl.d2, pl.records) * sizeof(float));
+    w.res_out = c.take<float>(pl.N * pl.C_out * 8);
+    const size_t f1 = pl.records ? forward_workspace_bytes(&pl.d1, pl.kind) : 0, f2 = pl.records ? forward_workspace_bytes(&pl.d2, pl.kind) : 0;
+    w.conv = c.take(f1 > f2 ? f1 : f2, &w.conv_bytes);
+    return w;
+}
+
+// (the convolutions' gW_eff tensors are not wanted, so they have no piece: fc_backward_all pulls the partial sums back to the parameters)
+struct ResnetBwdWs { float *g_pre2, *g_h, *g_pre1, *part1, *part2; void *lin, *conv; size_t part1_bytes, part2_bytes, lin_bytes, conv_bytes; };
+static ResnetBwdWs resnet_bwd_ws(Carver& c, const ResnetPlan& pl) {
+    ResnetBwdWs w;
+    const int N = (int)pl.N;
+    w.g_pre2 = c.take<float>(pl.N * pl.C_out * 8);
+    w.g_h = c.take<float>(pl.N * pl.C_mid * 8);
+    w.g_pre1 = c.take<float>(pl.N * pl.C_mid * 8);
+    w.part1 = c.take<float>(fc_tangent_nonlin_backward_workspace_bytes(N, pl.C_mid), &w.part1_bytes);
+    w.part2 = c.take<float>(fc_tangent_nonlin_backward_workspace_bytes(N, pl.C_out), &w.part2_bytes);
+    w.lin = c.take(fc_tangent_lin_backward_workspace_bytes(N, pl.C_in, pl.C_out), &w.lin_bytes);
+    const size_t b1 = backward_workspace_bytes(&pl.d1), b2 = backward_workspace_bytes(&pl.d2);
+    w.conv = c.take(b1 > b2 ? b1 : b2, &w.conv_bytes);
+    return w;
 }
 
 static bool filter_params_ok(const fc_filter_params& f, bool backward) {
@@ -100,13 +101,13 @@ extern "C" {
 
 size_t fc_resnet_block_saved_bytes(const fc_mesh* mesh, const fc_resnet_block_params* p) {
     fc::ResnetPlan pl;
-    return fc::resnet_plan(mesh, p, pl) ? pl.saved : 0;
+    return fc::resnet_plan(mesh, p, pl) ? fc::carved_bytes(fc::resnet_saved, pl) : 0;
 }
 
 size_t fc_resnet_block_workspace_bytes(const fc_mesh* mesh, const fc_resnet_block_params* p, int32_t backward) {
     fc::ResnetPlan pl;
     if (!fc::resnet_plan(mesh, p, pl)) return 0;
-    return backward ? pl.ws_bwd : pl.ws_fwd;
+    return backward ? fc::carved_bytes(fc::resnet_bwd_ws, pl) : fc::carved_bytes(fc::resnet_fwd_ws, pl);
 }
 
 int fc_resnet_block_forward(const float* x, const fc_mesh* mesh, const fc_resnet_block_params* p, float* out, void* saved,
@@ -116,31 +117,25 @@ int fc_resnet_block_forward(const float* x, const fc_mesh* mesh, const fc_resnet
         return FC_ERR_BAD_ARGUMENT;
     fc::ResnetPlan pl;
     if (!fc::resnet_plan(mesh, p, pl)) return FC_ERR_UNSUPPORTED;
-    if (!saved || saved_bytes < pl.saved || !workspace || workspace_bytes < pl.ws_fwd) return FC_ERR_WORKSPACE;
+    if (!saved || saved_bytes < fc::carved_bytes(fc::resnet_saved, pl) || !workspace || workspace_bytes < fc::carved_bytes(fc::resnet_fwd_ws, pl))
+        return FC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     fc::Carver sv(saved), ws(workspace);
-    float* pre1 = sv.take(pl.pre1);
-    float* act1 = sv.take(pl.act1);
-    float* pre2 = sv.take(pl.pre2);
-    float* wpk_b1 = sv.take(pl.wpk_b1);
-    float* wpk_b2 = sv.take(pl.wpk_b2);
-    float* wpk_f1 = ws.take(pl.wpk_f1);
-    float* wpk_f2 = ws.take(pl.wpk_f2);
-    float* res_out = ws.take(pl.res_out);
-    void* fws = ws.take(pl.fwd_ws);
+    const fc::ResnetSaved s = fc::resnet_saved(sv, pl);
+    const fc::ResnetFwdWs w = fc::resnet_fwd_ws(ws, pl);
     // both convolutions' filter images (forward and backward) from one launch: the parameters are all known now
-    int rc = fc::pack_filter_params_pair_impl(p->conv1, wpk_f1, wpk_b1, &pl.d1, p->conv2, wpk_f2, wpk_b2, &pl.d2, pl.records, st);
+    int rc = fc::pack_filter_params_pair_impl(p->conv1, w.wpk_f1, s.wpk_b1, &pl.d1, p->conv2, w.wpk_f2, s.wpk_b2, &pl.d2, pl.records, st);
     if (rc != FC_OK) return rc;
     // h = modReLU_1(conv1(x)): the modReLU in the convolution's epilogue (pre1 = the pre-activation its VJP needs)
-    fc_epilogue e1 = {nullptr, p->bias1, act1};
-    rc = fc::conv_forward(x, mesh, &pl.d1, p->conv1, wpk_f1, wpk_b1, pre1, &e1, fws, pl.fwd_ws, pl.records, st, true);
+    fc_epilogue e1 = {nullptr, p->bias1, s.act1};
+    rc = fc::conv_forward(x, mesh, &pl.d1, p->conv1, w.wpk_f1, s.wpk_b1, s.pre1, &e1, w.conv, w.conv_bytes, pl.records, st, true);
     if (rc != FC_OK) return rc;
     // res(x)
-    rc = fc_tangent_lin_forward(x, p->res_re, p->res_im, res_out, mesh->N, p->C_in, p->C_out, stream);
+    rc = fc_tangent_lin_forward(x, p->res_re, p->res_im, w.res_out, mesh->N, p->C_in, p->C_out, stream);
     if (rc != FC_OK) return rc;
     // out = modReLU_2(res(x) + conv2(h)): residual add and modReLU in conv2's epilogue
-    fc_epilogue e2 = {res_out, p->bias2, out};
-    return fc::conv_forward(act1, mesh, &pl.d2, p->conv2, wpk_f2, wpk_b2, pre2, &e2, fws, pl.fwd_ws, pl.records, st, true);
+    fc_epilogue e2 = {w.res_out, p->bias2, out};
+    return fc::conv_forward(s.act1, mesh, &pl.d2, p->conv2, w.wpk_f2, s.wpk_b2, s.pre2, &e2, w.conv, w.conv_bytes, pl.records, st, true);
 }
 
 int fc_resnet_block_backward(const float* x, const float* g_out, const fc_mesh* mesh, const fc_resnet_block_params* p, const void* saved,
@@ -151,42 +146,34 @@ int fc_resnet_block_backward(const float* x, const float* g_out, const fc_mesh* 
         return FC_ERR_BAD_ARGUMENT;
     fc::ResnetPlan pl;
     if (!fc::resnet_plan(mesh, p, pl)) return FC_ERR_UNSUPPORTED;
-    if (!saved || saved_bytes < pl.saved || !workspace || workspace_bytes < pl.ws_bwd) return FC_ERR_WORKSPACE;
+    if (!saved || saved_bytes < fc::carved_bytes(fc::resnet_saved, pl) || !workspace || workspace_bytes < fc::carved_bytes(fc::resnet_bwd_ws, pl))
+        return FC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    fc::Carver sv(const_cast<void*>(saved)), ws(workspace);
-    const float* pre1 = sv.take(pl.pre1);
-    const float* act1 = sv.take(pl.act1);
-    const float* pre2 = sv.take(pl.pre2);
-    const float* wpk_b1 = sv.take(pl.wpk_b1);
-    const float* wpk_b2 = sv.take(pl.wpk_b2);
-    float* g_pre2 = ws.take(pl.g_pre2);
-    float* g_h = ws.take(pl.g_h);
-    float* g_pre1 = ws.take(pl.g_pre1);
-    float* part1 = ws.take(pl.part1);
-    float* part2 = ws.take(pl.part2);
-    void* lin_ws = ws.take(pl.lin_ws);
-    void* cws = ws.take(pl.conv_ws);
+    fc::Carver sv(saved), ws(workspace);
+    const fc::ResnetSaved s = fc::resnet_saved(sv, pl);
+    const fc::ResnetBwdWs w = fc::resnet_bwd_ws(ws, pl);
     const int N = mesh->N;
     // modReLU_2: g_pre2 and the bias-gradient partials, which conv2's finishing launch sums (fc_filter_params' rider)
-    int rc = fc_tangent_nonlin_backward_partial(pre2, p->bias2, g_out, g_pre2, part2, pl.part2, N, p->C_out, stream);
+    int rc = fc_tangent_nonlin_backward_partial(s.pre2, p->bias2, g_out, w.g_pre2, w.part2, w.part2_bytes, N, p->C_out, stream);
     if (rc != FC_OK) return rc;
     fc_filter_params f2 = p->conv2;
-    f2.bias_partials = part2;
+    f2.bias_partials = w.part2;
     f2.bias_nparts = fc_tangent_nonlin_backward_groups(N);
     f2.g_bias = p->g_bias2;
-    rc = fc_backward_all(act1, g_pre2, mesh->bwd, mesh->by_source, pl.records, wpk_b2, g_h, nullptr, &f2, cws, pl.conv_ws, &pl.d2, stream);
+    rc = fc_backward_all(s.act1, w.g_pre2, mesh->bwd, mesh->by_source, pl.records, s.wpk_b2, w.g_h, nullptr, &f2, w.conv, w.conv_bytes, &pl.d2,
+                         stream);
     if (rc != FC_OK) return rc;
     // modReLU_1 and conv1: gx = conv1's input gradient ...
-    rc = fc_tangent_nonlin_backward_partial(pre1, p->bias1, g_h, g_pre1, part1, pl.part1, N, p->C_mid, stream);
+    rc = fc_tangent_nonlin_backward_partial(s.pre1, p->bias1, w.g_h, w.g_pre1, w.part1, w.part1_bytes, N, p->C_mid, stream);
     if (rc != FC_OK) return rc;
     fc_filter_params f1 = p->conv1;
-    f1.bias_partials = part1;
+    f1.bias_partials = w.part1;
     f1.bias_nparts = fc_tangent_nonlin_backward_groups(N);
     f1.g_bias = p->g_bias1;
-    rc = fc_backward_all(x, g_pre1, mesh->bwd, mesh->by_source, pl.records, wpk_b1, gx, nullptr, &f1, cws, pl.conv_ws, &pl.d1, stream);
+    rc = fc_backward_all(x, w.g_pre1, mesh->bwd, mesh->by_source, pl.records, s.wpk_b1, gx, nullptr, &f1, w.conv, w.conv_bytes, &pl.d1, stream);
     if (rc != FC_OK) return rc;
     // ... plus the residual branch's (res sees the same cotangent as conv2: g_pre2), added by the TangentLin kernel itself
-    return fc::tangent_lin_backward_impl(x, g_pre2, p->res_re, p->res_im, gx, gx, p->g_res_re, p->g_res_im, lin_ws, pl.lin_ws, N, p->C_in,
+    return fc::tangent_lin_backward_impl(x, w.g_pre2, p->res_re, p->res_im, gx, gx, p->g_res_re, p->g_res_im, w.lin, w.lin_bytes, N, p->C_in,
                                          p->C_out, st);
 }
 
@@ -197,10 +184,8 @@ namespace fc {
 
 struct EchoPlan {
     fc_dims d;
-    int records, dS;
-    size_t pre, act, hist, wpk_b, saved;
-    size_t wpk_f, fwd_ws, ws_fwd;
-    size_t g_act, g_pre, part, gw, gh, conv_ws, ws_bwd;
+    int records, kind, dS, n_des;
+    size_t N;
 };
 
 static bool echo_plan(const fc_mesh* m, const fc_echo_block_params* p, EchoPlan& pl) {
@@ -210,23 +195,35 @@ static bool echo_plan(const fc_mesh* m, const fc_echo_block_params* p, EchoPlan&
     pl.d = conv_dims(m, p->C_in, p->n_des);
     if (!fc_supported(&pl.d)) return false;
     pl.records = m->kind != 0 ? 1 : 0;
-    const size_t N = (size_t)m->N;
-    pl.pre = blk_align(N * p->n_des * 8);
-    pl.act = pl.pre;
-    pl.hist = blk_align(N * p->n_des * pl.dS * 8);
-    pl.wpk_b = blk_align(packed_filter_floats_bwd(&pl.d, pl.records) * sizeof(float));
-    pl.saved = pl.pre + pl.act + pl.hist + pl.wpk_b;
-    pl.wpk_f = blk_align(packed_filter_floats_fwd(&pl.d, pl.records) * sizeof(float));
-    pl.fwd_ws = blk_align(pl.records ? forward_workspace_bytes(&pl.d, m->kind) : 0);
-    pl.ws_fwd = pl.wpk_f + pl.fwd_ws;
-    pl.g_act = pl.pre;
-    pl.g_pre = pl.pre;
-    pl.part = blk_align(fc_tangent_nonlin_backward_workspace_bytes(m->N, p->n_des));
-    pl.gw = 0;
-    pl.gh = pl.hist;
-    pl.conv_ws = blk_align(backward_workspace_bytes(&pl.d));
-    pl.ws_bwd = pl.g_act + pl.g_pre + pl.part + pl.gw + pl.gh + pl.conv_ws;
+    pl.kind = m->kind;
+    pl.n_des = p->n_des;
+    pl.N = (size_t)m->N;
     return true;
+}
+
+struct EchoSaved { float *pre, *act, *hist, *wpk_b; };
+static EchoSaved echo_saved(Carver& c, const EchoPlan& pl) {
+    return {c.take<float>(pl.N * pl.n_des * 8), c.take<float>(pl.N * pl.n_des * 8), c.take<float>(pl.N * pl.n_des * pl.dS * 8),
+            c.take<float>(packed_filter_floats_bwd(&pl.d, pl.records) * sizeof(float))};
+}
+
+struct EchoFwdWs { float* wpk_f; void* conv; size_t conv_bytes; };
+static EchoFwdWs echo_fwd_ws(Carver& c, const EchoPlan& pl) {
+    EchoFwdWs w;
+    w.wpk_f = c.take<float>(packed_filter_floats_fwd(&pl.d, pl.records) * sizeof(float));
+    w.conv = c.take(pl.records ? forward_workspace_bytes(&pl.d, pl.kind) : 0, &w.conv_bytes);
+    return w;
+}
+
+struct EchoBwdWs { float *g_act, *g_pre, *part, *gh; void* conv; size_t part_bytes, conv_bytes; };
+static EchoBwdWs echo_bwd_ws(Carver& c, const EchoPlan& pl) {
+    EchoBwdWs w;
+    w.g_act = c.take<float>(pl.N * pl.n_des * 8);
+    w.g_pre = c.take<float>(pl.N * pl.n_des * 8);
+    w.part = c.take<float>(fc_tangent_nonlin_backward_workspace_bytes((int)pl.N, pl.n_des), &w.part_bytes);
+    w.gh = c.take<float>(pl.N * pl.n_des * pl.dS * 8);
+    w.conv = c.take(backward_workspace_bytes(&pl.d), &w.conv_bytes);
+    return w;
 }
 
 }  // namespace fc
@@ -235,13 +232,13 @@ extern "C" {
 
 size_t fc_echo_block_saved_bytes(const fc_mesh* mesh, const fc_echo_block_params* p) {
     fc::EchoPlan pl;
-    return fc::echo_plan(mesh, p, pl) ? pl.saved : 0;
+    return fc::echo_plan(mesh, p, pl) ? fc::carved_bytes(fc::echo_saved, pl) : 0;
 }
 
 size_t fc_echo_block_workspace_bytes(const fc_mesh* mesh, const fc_echo_block_params* p, int32_t backward) {
     fc::EchoPlan pl;
     if (!fc::echo_plan(mesh, p, pl)) return 0;
-    return backward ? pl.ws_bwd : pl.ws_fwd;
+    return backward ? fc::carved_bytes(fc::echo_bwd_ws, pl) : fc::carved_bytes(fc::echo_fwd_ws, pl);
 }
 
 int fc_echo_block_forward(const float* x, const fc_mesh* mesh, const float* ln_t, const float* wxp_t, const fc_echo_block_params* p,
@@ -250,19 +247,16 @@ int fc_echo_block_forward(const float* x, const fc_mesh* mesh, const float* ln_t
     if (mesh->E > 0 && (!ln_t || !wxp_t || !mesh->by_target->nbr)) return FC_ERR_BAD_ARGUMENT;
     fc::EchoPlan pl;
     if (!fc::echo_plan(mesh, p, pl)) return FC_ERR_UNSUPPORTED;
-    if (!saved || saved_bytes < pl.saved || !workspace || workspace_bytes < pl.ws_fwd) return FC_ERR_WORKSPACE;
+    if (!saved || saved_bytes < fc::carved_bytes(fc::echo_saved, pl) || !workspace || workspace_bytes < fc::carved_bytes(fc::echo_fwd_ws, pl))
+        return FC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     fc::Carver sv(saved), ws(workspace);
-    float* pre = sv.take(pl.pre);
-    float* act = sv.take(pl.act);
-    float* hist = sv.take(pl.hist);
-    float* wpk_b = sv.take(pl.wpk_b);
-    float* wpk_f = ws.take(pl.wpk_f);
-    void* fws = ws.take(pl.fwd_ws);
-    fc_epilogue e = {nullptr, p->bias, act};
-    int rc = fc::conv_forward(x, mesh, &pl.d, p->conv, wpk_f, wpk_b, pre, &e, fws, pl.fwd_ws, pl.records, st);
+    const fc::EchoSaved s = fc::echo_saved(sv, pl);
+    const fc::EchoFwdWs w = fc::echo_fwd_ws(ws, pl);
+    fc_epilogue e = {nullptr, p->bias, s.act};
+    int rc = fc::conv_forward(x, mesh, &pl.d, p->conv, w.wpk_f, s.wpk_b, s.pre, &e, w.conv, w.conv_bytes, pl.records, st);
     if (rc != FC_OK) return rc;
-    return fc_echo_forward(act, ln_t, wxp_t, mesh->by_target, hist, desc, mesh->N, mesh->E, p->n_des, p->n_bins, stream);
+    return fc_echo_forward(s.act, ln_t, wxp_t, mesh->by_target, s.hist, desc, mesh->N, mesh->E, p->n_des, p->n_bins, stream);
 }
 
 int fc_echo_block_backward(const float* x, const float* g_desc, const fc_mesh* mesh, const float* ln_s, const float* wxp_s,
@@ -273,27 +267,21 @@ int fc_echo_block_backward(const float* x, const float* g_desc, const fc_mesh* m
     if (mesh->E > 0 && (!ln_s || !wxp_s || !mesh->by_source->nbr)) return FC_ERR_BAD_ARGUMENT;
     fc::EchoPlan pl;
     if (!fc::echo_plan(mesh, p, pl)) return FC_ERR_UNSUPPORTED;
-    if (!saved || saved_bytes < pl.saved || !workspace || workspace_bytes < pl.ws_bwd) return FC_ERR_WORKSPACE;
-    fc::Carver sv(const_cast<void*>(saved)), ws(workspace);
-    const float* pre = sv.take(pl.pre);
-    const float* act = sv.take(pl.act);
-    const float* hist = sv.take(pl.hist);
-    const float* wpk_b = sv.take(pl.wpk_b);
-    float* g_act = ws.take(pl.g_act);
-    float* g_pre = ws.take(pl.g_pre);
-    float* part = ws.take(pl.part);
-    float* gh = ws.take(pl.gh);
-    void* cws = ws.take(pl.conv_ws);
+    if (!saved || saved_bytes < fc::carved_bytes(fc::echo_saved, pl) || !workspace || workspace_bytes < fc::carved_bytes(fc::echo_bwd_ws, pl))
+        return FC_ERR_WORKSPACE;
+    fc::Carver sv(saved), ws(workspace);
+    const fc::EchoSaved s = fc::echo_saved(sv, pl);
+    const fc::EchoBwdWs w = fc::echo_bwd_ws(ws, pl);
     const int N = mesh->N;
-    int rc = fc_echo_backward(act, ln_s, wxp_s, mesh->by_source, hist, g_desc, g_act, gh, N, mesh->E, p->n_des, p->n_bins, stream);
+    int rc = fc_echo_backward(s.act, ln_s, wxp_s, mesh->by_source, s.hist, g_desc, w.g_act, w.gh, N, mesh->E, p->n_des, p->n_bins, stream);
     if (rc != FC_OK) return rc;
-    rc = fc_tangent_nonlin_backward_partial(pre, p->bias, g_act, g_pre, part, pl.part, N, p->n_des, stream);
+    rc = fc_tangent_nonlin_backward_partial(s.pre, p->bias, w.g_act, w.g_pre, w.part, w.part_bytes, N, p->n_des, stream);
     if (rc != FC_OK) return rc;
     fc_filter_params f = p->conv;
-    f.bias_partials = part;
+    f.bias_partials = w.part;
     f.bias_nparts = fc_tangent_nonlin_backward_groups(N);
     f.g_bias = p->g_bias;
-    return fc_backward_all(x, g_pre, mesh->bwd, mesh->by_source, pl.records, wpk_b, gx, nullptr, &f, cws, pl.conv_ws, &pl.d, stream);
+    return fc_backward_all(x, w.g_pre, mesh->bwd, mesh->by_source, pl.records, s.wpk_b, gx, nullptr, &f, w.conv, w.conv_bytes, &pl.d, stream);
 }
 
 }  // extern "C"
@@ -301,24 +289,24 @@ int fc_echo_block_backward(const float* x, const float* g_desc, const fc_mesh* m
 // ---- LiftBlock --------------------------------------------------------------------------------------------------------------
 namespace fc {
 
-struct LiftPlan {
-    size_t pre, ang, mag, s1sum, saved;
-    size_t g_pre, nl_ws, tf_ws, ws_bwd;
-};
+static bool lift_valid(const fc_mesh* m, const fc_lift_block_params* p) {
+    return m && m->N > 0 && m->E >= 0 && m->R > 0 && m->by_target && m->by_source && p && p->C_in > 0 && p->C_out > 0;
+}
 
-static bool lift_plan(const fc_mesh* m, const fc_lift_block_params* p, LiftPlan& pl) {
-    if (!m || m->N <= 0 || m->E < 0 || m->R <= 0 || !m->by_target || !m->by_source || !p || p->C_in <= 0 || p->C_out <= 0) return false;
+struct LiftSaved { float *pre, *ang, *mag, *s1sum; };
+static LiftSaved lift_saved(Carver& c, const fc_mesh* m, const fc_lift_block_params* p) {
     const size_t N = (size_t)m->N;
-    pl.pre = blk_align(N * p->C_out * 8);
-    pl.ang = blk_align(N * p->C_in * m->R * 8);
-    pl.mag = blk_align(N * p->C_in * m->R * 4);
-    pl.s1sum = blk_align(N * m->R * 8);
-    pl.saved = pl.pre + pl.ang + pl.mag + pl.s1sum;
-    pl.g_pre = pl.pre;
-    pl.nl_ws = blk_align(fc_tangent_nonlin_backward_workspace_bytes(m->N, p->C_out));
-    pl.tf_ws = blk_align(fc_trans_field_backward_workspace_bytes(m->N, p->C_in, p->C_out, m->R));
-    pl.ws_bwd = pl.g_pre + pl.nl_ws + pl.tf_ws;
-    return true;
+    return {c.take<float>(N * p->C_out * 8), c.take<float>(N * p->C_in * m->R * 8), c.take<float>(N * p->C_in * m->R * 4),
+            c.take<float>(N * m->R * 8)};
+}
+
+struct LiftBwdWs { float* g_pre; void *nl, *tf; size_t nl_bytes, tf_bytes; };
+static LiftBwdWs lift_bwd_ws(Carver& c, const fc_mesh* m, const fc_lift_block_params* p) {
+    LiftBwdWs w;
+    w.g_pre = c.take<float>((size_t)m->N * p->C_out * 8);
+    w.nl = c.take(fc_tangent_nonlin_backward_workspace_bytes(m->N, p->C_out), &w.nl_bytes);
+    w.tf = c.take(fc_trans_field_backward_workspace_bytes(m->N, p->C_in, p->C_out, m->R), &w.tf_bytes);
+    return w;
 }
 
 }  // namespace fc
@@ -326,53 +314,41 @@ static bool lift_plan(const fc_mesh* m, const fc_lift_block_params* p, LiftPlan&
 extern "C" {
 
 size_t fc_lift_block_saved_bytes(const fc_mesh* mesh, const fc_lift_block_params* p) {
-    fc::LiftPlan pl;
-    return fc::lift_plan(mesh, p, pl) ? pl.saved : 0;
+    return fc::lift_valid(mesh, p) ? fc::carved_bytes(fc::lift_saved, mesh, p) : 0;
 }
 
 size_t fc_lift_block_workspace_bytes(const fc_mesh* mesh, const fc_lift_block_params* p, int32_t backward) {
-    fc::LiftPlan pl;
-    if (!fc::lift_plan(mesh, p, pl)) return 0;
-    return backward ? pl.ws_bwd : 0;
+    return fc::lift_valid(mesh, p) && backward ? fc::carved_bytes(fc::lift_bwd_ws, mesh, p) : 0;
 }
 
 int fc_lift_block_forward(const float* x, const float* lift_sten, int32_t sten_stride, const fc_mesh* mesh, const int64_t* slot_to_edge_t,
                           const fc_lift_block_params* p, float* out, void* saved, size_t saved_bytes, void* stream) {
-    fc::LiftPlan pl;
-    if (!x || !out || !fc::lift_plan(mesh, p, pl) || !p->zonal_ang || !p->zonal_mag || !p->phase || !p->bias) return FC_ERR_BAD_ARGUMENT;
-    if (!saved || saved_bytes < pl.saved) return FC_ERR_WORKSPACE;
+    if (!x || !out || !fc::lift_valid(mesh, p) || !p->zonal_ang || !p->zonal_mag || !p->phase || !p->bias) return FC_ERR_BAD_ARGUMENT;
+    if (!saved || saved_bytes < fc::carved_bytes(fc::lift_saved, mesh, p)) return FC_ERR_WORKSPACE;
     fc::Carver sv(saved);
-    float* pre = sv.take(pl.pre);
-    float* ang = sv.take(pl.ang);
-    float* mag = sv.take(pl.mag);
-    float* s1sum = sv.take(pl.s1sum);
-    int rc = fc_trans_field_forward(x, lift_sten, mesh->by_target, slot_to_edge_t, p->zonal_ang, p->zonal_mag, p->phase, pre, ang, mag, s1sum,
-                                    mesh->N, mesh->E, p->C_in, p->C_out, mesh->R, sten_stride, stream);
+    const fc::LiftSaved s = fc::lift_saved(sv, mesh, p);
+    int rc = fc_trans_field_forward(x, lift_sten, mesh->by_target, slot_to_edge_t, p->zonal_ang, p->zonal_mag, p->phase, s.pre, s.ang, s.mag,
+                                    s.s1sum, mesh->N, mesh->E, p->C_in, p->C_out, mesh->R, sten_stride, stream);
     if (rc != FC_OK) return rc;
-    return fc_tangent_nonlin_forward(pre, p->bias, out, mesh->N, p->C_out, stream);
+    return fc_tangent_nonlin_forward(s.pre, p->bias, out, mesh->N, p->C_out, stream);
 }
 
 int fc_lift_block_backward(const float* g_out, const float* lift_sten, int32_t sten_stride, const fc_mesh* mesh, const int64_t* slot_to_edge_s,
                            const fc_lift_block_params* p, const void* saved, size_t saved_bytes, float* gx, void* workspace,
                            size_t workspace_bytes, void* stream) {
-    fc::LiftPlan pl;
-    if (!g_out || !gx || !fc::lift_plan(mesh, p, pl) || !p->zonal_ang || !p->zonal_mag || !p->phase || !p->bias || !p->g_zonal_ang ||
+    if (!g_out || !gx || !fc::lift_valid(mesh, p) || !p->zonal_ang || !p->zonal_mag || !p->phase || !p->bias || !p->g_zonal_ang ||
         !p->g_zonal_mag || !p->g_bias || (p->ftype != 0 && !p->g_phase))
         return FC_ERR_BAD_ARGUMENT;
-    if (!saved || saved_bytes < pl.saved || !workspace || workspace_bytes < pl.ws_bwd) return FC_ERR_WORKSPACE;
-    fc::Carver sv(const_cast<void*>(saved)), ws(workspace);
-    const float* pre = sv.take(pl.pre);
-    const float* ang = sv.take(pl.ang);
-    const float* mag = sv.take(pl.mag);
-    const float* s1sum = sv.take(pl.s1sum);
-    float* g_pre = ws.take(pl.g_pre);
-    void* nl_ws = ws.take(pl.nl_ws);
-    void* tf_ws = ws.take(pl.tf_ws);
-    int rc = fc_tangent_nonlin_backward(pre, p->bias, g_out, g_pre, p->g_bias, nl_ws, pl.nl_ws, mesh->N, p->C_out, stream);
+    if (!saved || saved_bytes < fc::carved_bytes(fc::lift_saved, mesh, p) || !workspace || workspace_bytes < fc::carved_bytes(fc::lift_bwd_ws, mesh, p))
+        return FC_ERR_WORKSPACE;
+    fc::Carver sv(saved), ws(workspace);
+    const fc::LiftSaved s = fc::lift_saved(sv, mesh, p);
+    const fc::LiftBwdWs w = fc::lift_bwd_ws(ws, mesh, p);
+    int rc = fc_tangent_nonlin_backward(s.pre, p->bias, g_out, w.g_pre, p->g_bias, w.nl, w.nl_bytes, mesh->N, p->C_out, stream);
     if (rc != FC_OK) return rc;
-    return fc_trans_field_backward(lift_sten, mesh->by_source, slot_to_edge_s, p->zonal_ang, p->zonal_mag, p->phase, ang, mag, s1sum, g_pre, gx,
-                                   p->g_zonal_ang, p->g_zonal_mag, p->ftype != 0 ? p->g_phase : nullptr, tf_ws, pl.tf_ws, mesh->N, mesh->E,
-                                   p->C_in, p->C_out, mesh->R, sten_stride, p->ftype, stream);
+    return fc_trans_field_backward(lift_sten, mesh->by_source, slot_to_edge_s, p->zonal_ang, p->zonal_mag, p->phase, s.ang, s.mag, s.s1sum,
+                                   w.g_pre, gx, p->g_zonal_ang, p->g_zonal_mag, p->ftype != 0 ? p->g_phase : nullptr, w.tf, w.tf_bytes,
+                                   mesh->N, mesh->E, p->C_in, p->C_out, mesh->R, sten_stride, p->ftype, stream);
 }
 
 }  // extern "C"

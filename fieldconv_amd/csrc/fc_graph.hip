@@ -17,6 +17,7 @@
 #include <hipcub/hipcub.hpp>
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -375,29 +376,29 @@ __global__ __launch_bounds__(256) void graph_place_kernel(
     }
 }
 
-static size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-struct GraphPlan {
-    size_t cnt, deg, keys, ids, longs, rec, geo, cub, total;
-    size_t cub_bytes;
+// pairs of arrays share a piece: cnt = cnt_t | cnt_s (8 N each), deg = deg_t | deg_s (N+1 each), keys = key_t | key_s, ids = arrival
+// index (later the ordered ids) t | s, then ids in arrival order t | s, `ke` elements apart; the entry point derives the second halves
+struct GraphWs {
+    int32_t *long_runs, *cnt, *deg; uint32_t *keys, *ids; float *rec, *geo; void* cub;
+    size_t ke, cub_bytes, fill_bytes;           // fill_bytes: from long_runs to the end of the bucket counts, which one memset clears
 };
 
-static GraphPlan plan_graph(int N, int E, int recf, bool with_sten) {
-    GraphPlan p;
-    size_t scan_bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int32_t*)nullptr, (int32_t*)nullptr, N + 1);
-    p.cub_bytes = scan_bytes;
-    size_t off = 0;
-    p.longs = off; off += align256(((size_t)N * 16 + 1) * 4);          // count + list of the runs longer than kShortRun
-    p.cnt = off;   off += align256((size_t)N * 8 * 4 * 2);             // cnt_t | cnt_s
-    p.deg = off;   off += align256((size_t)(N + 1) * 4 * 2);           // deg_t | deg_s
-    p.keys = off;  off += align256((size_t)E * 4) * 2;                 // key_t | key_s
-    p.ids = off;   off += align256((size_t)E * 4) * 4;                 // arrival index, later ordered ids: t | s; ids in arrival order: t | s
-    p.rec = off;   off += with_sten ? align256((size_t)E * recf * 4) : 0;
-    p.geo = off;   off += with_sten ? align256((size_t)E * 8 * 4) : 0;
-    p.cub = off;   off += align256(p.cub_bytes);
-    p.total = off + 256;
-    return p;
+static GraphWs graph_ws(Carver& c, int N, int E, int recf, bool with_sten) {
+    GraphWs w;
+    w.cub_bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, w.cub_bytes, (const int32_t*)nullptr, (int32_t*)nullptr, N + 1);
+    w.ke = align256((size_t)E * 4) / 4;
+    w.long_runs = c.take<int32_t>(((size_t)N * 16 + 1) * 4);        // count + list of the runs longer than kShortRun
+    w.fill_bytes = c.used + (size_t)N * 8 * 4 * 2;                  // (long_runs is the first piece, cnt adjacent to it)
+    w.cnt = c.take<int32_t>((size_t)N * 8 * 4 * 2);
+    w.deg = c.take<int32_t>((size_t)(N + 1) * 4 * 2);
+    w.keys = c.take<uint32_t>(w.ke * 4 * 2);
+    w.ids = c.take<uint32_t>(w.ke * 4 * 4);
+    w.rec = with_sten ? c.take<float>((size_t)E * recf * 4) : nullptr;
+    w.geo = with_sten ? c.take<float>((size_t)E * 8 * 4) : nullptr;
+    w.cub = c.take(w.cub_bytes);
+    c.take(256);                                                    // slack behind the last piece
+    return w;
 }
 
 }  // namespace fc
@@ -407,7 +408,7 @@ extern "C" {
 size_t fc_graph_workspace_bytes(int32_t N, int32_t E, int32_t R, int32_t F, int32_t with_stencil) {
     if (N <= 0 || E < 0) return 0;
     const int recf = (4 + 2 * F + 3) / 4 * 4;
-    return fc::plan_graph(N, E, recf, with_stencil != 0).total;
+    return fc::carved_bytes(fc::graph_ws, N, E, recf, with_stencil != 0);
 }
 
 // pad_rec / pad_geo: rows behind the E-th of rec_t, rec_s / geo_t that are zero-filled
@@ -421,31 +422,19 @@ static int graph_build_impl(const int64_t* supp_edges, const float* supp_sten, c
     const bool with_sten = supp_sten != nullptr || factors != nullptr;
     if (with_sten && (R < 2 || R > fc::kGraphMaxR || F < 1 || F > fc::kGraphMaxF || (F & 1) == 0 || !rec_t || !rec_s)) return FC_ERR_UNSUPPORTED;
     const int recf = (4 + 2 * F + 3) / 4 * 4;
-    const fc::GraphPlan p = fc::plan_graph(N, E, recf, with_sten);
-    if (workspace_bytes < p.total) return FC_ERR_WORKSPACE;
+    if (workspace_bytes < fc::carved_bytes(fc::graph_ws, N, E, recf, with_sten)) return FC_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace);
-    int32_t* cnt_t = reinterpret_cast<int32_t*>(w + p.cnt);
-    int32_t* cnt_s = cnt_t + (size_t)N * 8;
-    int32_t* deg_t = reinterpret_cast<int32_t*>(w + p.deg);
-    int32_t* deg_s = deg_t + (N + 1);
-    const size_t ke = (((size_t)E * 4 + 255) / 256 * 256) / 4;
-    uint32_t* key_t = reinterpret_cast<uint32_t*>(w + p.keys);
-    uint32_t* key_s = key_t + ke;
-    uint32_t* arr_t = reinterpret_cast<uint32_t*>(w + p.ids);         // arrival indices; the ordered ids take their place
-    uint32_t* arr_s = arr_t + ke;
-    uint32_t* raw_t = arr_s + ke;
-    uint32_t* raw_s = raw_t + ke;
-    int32_t* long_runs = reinterpret_cast<int32_t*>(w + p.longs);
-    float* rec = with_sten ? reinterpret_cast<float*>(w + p.rec) : nullptr;
-    float* geo = (with_sten && geo_t) ? reinterpret_cast<float*>(w + p.geo) : nullptr;
-    void* cub = w + p.cub;
-    size_t cub_bytes = p.cub_bytes;
+    fc::Carver ws(workspace);
+    const fc::GraphWs g = fc::graph_ws(ws, N, E, recf, with_sten);
+    int32_t *cnt_t = g.cnt, *cnt_s = cnt_t + (size_t)N * 8, *deg_t = g.deg, *deg_s = deg_t + (N + 1), *long_runs = g.long_runs;
+    uint32_t *key_t = g.keys, *key_s = key_t + g.ke, *arr_t = g.ids, *arr_s = arr_t + g.ke, *raw_t = arr_s + g.ke, *raw_s = raw_t + g.ke;
+    float *rec = g.rec, *geo = geo_t ? g.geo : nullptr;
+    size_t cub_bytes = g.cub_bytes;
     if (pad_rec < 0 || pad_geo < 0) return FC_ERR_BAD_ARGUMENT;
     const fc::GraphArgs a{N, E, R, F, recf, pad_rec, pad_geo};
 
     // one fill: the long-run list (its counter is what matters) and the bucket counts are adjacent
-    if (hipMemsetAsync(w + p.longs, 0, (p.cnt - p.longs) + (size_t)N * 8 * 4 * 2, s) != hipSuccess) return FC_ERR_LAUNCH;
+    if (hipMemsetAsync(long_runs, 0, g.fill_bytes, s) != hipSuccess) return FC_ERR_LAUNCH;
     if (hipMemsetAsync(flags, 0, 4, s) != hipSuccess) return FC_ERR_LAUNCH;
     if (factors) {
         if (factors->E_in > 0)
@@ -457,9 +446,9 @@ static int graph_build_impl(const int64_t* supp_edges, const float* supp_sten, c
                            reinterpret_cast<const float2*>(supp_sten), rec, geo, key_t, key_s, arr_t, arr_s, cnt_t, cnt_s, flags, a);
     }
     hipLaunchKernelGGL(fc::graph_runs_kernel, dim3((N + 1 + 255) / 256), dim3(256), 0, s, cnt_t, cnt_s, runs_t, runs_s, deg_t, deg_s, N);
-    if (hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, deg_t, rowptr_t, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
-    cub_bytes = p.cub_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, deg_s, rowptr_s, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
+    if (hipcub::DeviceScan::ExclusiveSum(g.cub, cub_bytes, deg_t, rowptr_t, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
+    cub_bytes = g.cub_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(g.cub, cub_bytes, deg_s, rowptr_s, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
     if (E > 0) {
         hipLaunchKernelGGL(fc::graph_scatter_kernel, dim3((E + 255) / 256), dim3(256), 0, s, key_t, key_s, arr_t, arr_s, rowptr_t, rowptr_s,
                            runs_t, runs_s, raw_t, raw_s, E);
@@ -499,18 +488,14 @@ int fc_precomp_graph(const float* log_mag, const float* log_ang, const float* xp
     if (!supp_edges_out || !ln || !wxp || !factors || !(epsilon > 0.f)) return FC_ERR_BAD_ARGUMENT;
     if (precomp_workspace_bytes < fc_precomp_workspace_bytes(N, E)) return FC_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // layout of the selection left by fc_precomp_mark (csrc/fc_precomp.hip): keep | pos | total (N)
-    const size_t seg = ((size_t)(E + 2) * 4 + 255) / 256 * 256;
-    char* wsp = static_cast<char*>(precomp_workspace);
+    fc::Carver pws(precomp_workspace);
+    const fc::PrecompSelection sel = fc::precomp_selection(pws, N, E);           // left by fc_precomp_mark
     fc::FactorArgs fa;
     fa.log_mag = log_mag; fa.log_ang = log_ang; fa.xp = reinterpret_cast<const float2*>(xp); fa.w = w; fa.edges_in = supp_edges;
-    fa.keep = reinterpret_cast<const int32_t*>(wsp);
-    fa.pos = reinterpret_cast<const int32_t*>(wsp + seg);
-    float* total = reinterpret_cast<float*>(wsp + 2 * seg);
-    fa.total = total;
+    fa.keep = sel.keep; fa.pos = sel.pos; fa.total = sel.total;
     fa.eps = epsilon; fa.E_in = E;
     fa.edges_out = supp_edges_out; fa.ln = reinterpret_cast<float2*>(ln); fa.wxp = reinterpret_cast<float2*>(wxp); fa.factors = factors;
-    const int rc = fc::precomp_area_sums(supp_edges, fa.keep, w, total, N, E, s);
+    const int rc = fc::precomp_area_sums(supp_edges, fa.keep, w, sel.total, N, E, s);
     if (rc != FC_OK) return rc;
     return graph_build_impl(supp_edges_out, nullptr, &fa, N, E_kept, rec_pad_rows, geo_pad_rows, R, F, rowptr_t, nbr_t, runs_t, perm_t, rowptr_s, nbr_s, runs_s, perm_s,
                             rec_t, rec_s, geo_t, flags, graph_workspace, graph_workspace_bytes, stream);

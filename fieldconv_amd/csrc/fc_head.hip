@@ -19,6 +19,7 @@
 // Everything lives in caller-owned buffers; sums run in a fixed order (deterministic).
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -577,12 +578,13 @@ static bool head_dims_ok(const fc_echo_head_params* p, int N) {
            p->C_out > 0 && p->C_out <= kHdMaxQ;
 }
 static HeadDims head_dims(const fc_echo_head_params* p, int N) { return HeadDims{N, p->D, p->H1, p->H2, p->C_in, p->C_out}; }
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
-// the backward pass's products and where their partials lie in the workspace
+// forward workspace: the slices of the first product, needed only when it is split
+static float* head_fwd_ws(Carver& c, const RgProblem& g) { return g.slices > 1 ? c.take<float>((size_t)g.slices * g.M * g.N * 4) : nullptr; }
+
+// the backward pass's products
 struct HeadBwdPlan {
     RgProblem gd, gw1, gw2, gw3, gwr;
-    size_t off_gh2, off_bias, off_p1, off_p2, off_p3, off_pr, total;
     int tiles;
 };
 static HeadBwdPlan head_bwd_plan(const fc_echo_head_params* p, int N) {
@@ -596,15 +598,18 @@ static HeadBwdPlan head_bwd_plan(const fc_echo_head_params* p, int N) {
     pl.gw3 = rg_problem(nullptr, nullptr, Q, H2, N, 1, Q, H2, 1);           // g^T h2
     pl.gwr = rg_problem(nullptr, nullptr, Q, C, N, 1, Q, C, 1, true);       // g^T softAbs(x)
     pl.tiles = (N + 15) / 16;
-    size_t off = 0;
-    pl.off_gh2 = off;  off += al256((size_t)N * H2 * 4);
-    pl.off_bias = off; off += al256((size_t)pl.tiles * (H1 + H2 + Q) * 4);
-    pl.off_p1 = off;   off += al256((size_t)pl.gw1.slices * H1 * D * 4);
-    pl.off_p2 = off;   off += al256((size_t)pl.gw2.slices * H2 * H1 * 4);
-    pl.off_p3 = off;   off += al256((size_t)pl.gw3.slices * Q * H2 * 4);
-    pl.off_pr = off;   off += al256((size_t)pl.gwr.slices * Q * C * 4);
-    pl.total = off;
     return pl;
+}
+
+// ... and where their partials lie in the workspace (part: the slices of gw1, gw2, gw3, gwr)
+struct HeadBwdWs { float *g_h2, *bias_part, *part[4]; };
+static HeadBwdWs head_bwd_ws(Carver& c, const fc_echo_head_params* p, int N, const HeadBwdPlan& pl) {
+    HeadBwdWs w;
+    w.g_h2 = c.take<float>((size_t)N * p->H2 * 4);
+    w.bias_part = c.take<float>((size_t)pl.tiles * (p->H1 + p->H2 + p->C_out) * 4);
+    const RgProblem* g[4] = {&pl.gw1, &pl.gw2, &pl.gw3, &pl.gwr};
+    for (int q = 0; q < 4; ++q) w.part[q] = c.take<float>((size_t)g[q]->slices * g[q]->M * g[q]->N * 4);
+    return w;
 }
 
 }  // namespace fc
@@ -613,8 +618,7 @@ extern "C" {
 
 size_t fc_echo_head_forward_workspace_bytes(int32_t N, const fc_echo_head_params* p) {
     if (!fc::head_dims_ok(p, N)) return 0;
-    const fc::RgProblem g = fc::rg_problem(nullptr, nullptr, N, p->H1, p->D, p->D, 1, 1, p->D);
-    return g.slices > 1 ? fc::al256((size_t)g.slices * N * p->H1 * 4) : 0;
+    return fc::carved_bytes(fc::head_fwd_ws, fc::rg_problem(nullptr, nullptr, N, p->H1, p->D, p->D, 1, 1, p->D));
 }
 
 int fc_echo_head_forward(const float* d, const float* x, const fc_echo_head_params* p, float* h1, float* h2, float* y, void* workspace,
@@ -628,8 +632,10 @@ int fc_echo_head_forward(const float* d, const float* x, const fc_echo_head_para
     ra.count = 1;
     ra.p[0] = fc::rg_problem(d, p->w1, N, p->H1, p->D, p->D, 1, 1, p->D);
     const bool split = ra.p[0].slices > 1;
-    if (split && (!workspace || workspace_bytes < fc_echo_head_forward_workspace_bytes(N, p))) return FC_ERR_WORKSPACE;
-    ra.p[0].C = split ? static_cast<float*>(workspace) : h1;
+    if (split && (!workspace || workspace_bytes < fc::carved_bytes(fc::head_fwd_ws, ra.p[0]))) return FC_ERR_WORKSPACE;
+    fc::Carver ws(workspace);
+    float* slices = fc::head_fwd_ws(ws, ra.p[0]);
+    ra.p[0].C = split ? slices : h1;
     ra.p[0].bias = p->b1;
     ra.p[0].relu = 1;
     int rc = fc::rg_launch(ra, s);
@@ -637,7 +643,7 @@ int fc_echo_head_forward(const float* d, const float* x, const fc_echo_head_para
     if (split) {
         fc::RfArgs fa{};
         fa.count = 1;
-        fa.t[0] = fc::RfTask{static_cast<const float*>(workspace), h1, nullptr, p->b1, (long)N * p->H1, (long)N * p->H1, ra.p[0].slices, p->H1, 1, 0, 0};
+        fa.t[0] = fc::RfTask{slices, h1, nullptr, p->b1, (long)N * p->H1, (long)N * p->H1, ra.p[0].slices, p->H1, 1, 0, 0};
         rc = fc::rf_launch(fa, s);
         if (rc != FC_OK) return rc;
     }
@@ -649,7 +655,7 @@ int fc_echo_head_forward(const float* d, const float* x, const fc_echo_head_para
 
 size_t fc_echo_head_backward_workspace_bytes(int32_t N, const fc_echo_head_params* p) {
     if (!fc::head_dims_ok(p, N)) return 0;
-    return fc::head_bwd_plan(p, N).total;
+    return fc::carved_bytes(fc::head_bwd_ws, p, N, fc::head_bwd_plan(p, N));
 }
 
 int fc_echo_head_backward(const float* d, const float* x, const float* h1, const float* h2, const float* g, const fc_echo_head_params* p,
@@ -659,23 +665,21 @@ int fc_echo_head_backward(const float* d, const float* x, const float* h1, const
         return FC_ERR_BAD_ARGUMENT;
     if (!fc::head_dims_ok(p, N)) return FC_ERR_UNSUPPORTED;
     fc::HeadBwdPlan pl = fc::head_bwd_plan(p, N);
-    if (!workspace || workspace_bytes < pl.total) return FC_ERR_WORKSPACE;
+    if (!workspace || workspace_bytes < fc::carved_bytes(fc::head_bwd_ws, p, N, pl)) return FC_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    float* g_h2 = reinterpret_cast<float*>(ws + pl.off_gh2);
-    float* bias_part = reinterpret_cast<float*>(ws + pl.off_bias);
+    fc::Carver ws(workspace);
+    const fc::HeadBwdWs w = fc::head_bwd_ws(ws, p, N, pl);
     const fc::HeadDims hd = fc::head_dims(p, N);
     const int H1 = p->H1, H2 = p->H2, C = p->C_in, Q = p->C_out, D = p->D;
     hipLaunchKernelGGL(fc::fc_head_bwd_kernel, dim3(pl.tiles), dim3(fc::kHdThreads), 0, s, g, h1, h2, reinterpret_cast<const float2*>(x), p->w2, p->w3,
-                       p->wr, g_h1, g_h2, reinterpret_cast<float2*>(gx), bias_part, hd);
+                       p->wr, g_h1, w.g_h2, reinterpret_cast<float2*>(gx), w.bias_part, hd);
     if (hipGetLastError() != hipSuccess) return FC_ERR_LAUNCH;
     // one grouped launch: g_d and the four weight gradients' slices
     fc::RgArgs ra{};
     ra.count = 5;
     ra.p[0] = pl.gd;  ra.p[0].A = g_h1; ra.p[0].B = p->w1; ra.p[0].C = g_d;
-    struct Wg { fc::RgProblem* g; const float* A; const float* B; size_t off; float* out; };
-    Wg wg[4] = {{&pl.gw1, g_h1, d, pl.off_p1, p->g_w1}, {&pl.gw2, g_h2, h1, pl.off_p2, p->g_w2}, {&pl.gw3, g, h2, pl.off_p3, p->g_w3},
-                {&pl.gwr, g, x, pl.off_pr, p->g_wr}};
+    struct Wg { fc::RgProblem* g; const float* A; const float* B; float* out; };
+    Wg wg[4] = {{&pl.gw1, g_h1, d, p->g_w1}, {&pl.gw2, w.g_h2, h1, p->g_w2}, {&pl.gw3, g, h2, p->g_w3}, {&pl.gwr, g, x, p->g_wr}};
     fc::RfArgs fa{};
     fa.count = 0;
     for (int q = 0; q < 4; ++q) {
@@ -683,19 +687,19 @@ int fc_echo_head_backward(const float* d, const float* x, const float* h1, const
         gp.A = wg[q].A;
         gp.B = wg[q].B;
         const bool split = gp.slices > 1;
-        gp.C = split ? reinterpret_cast<float*>(ws + wg[q].off) : wg[q].out;
+        gp.C = split ? w.part[q] : wg[q].out;
         ra.p[1 + q] = gp;
         if (split)
-            fa.t[fa.count++] = fc::RfTask{reinterpret_cast<const float*>(ws + wg[q].off), wg[q].out, nullptr, nullptr, (long)gp.M * gp.N,
+            fa.t[fa.count++] = fc::RfTask{w.part[q], wg[q].out, nullptr, nullptr, (long)gp.M * gp.N,
                                           (long)gp.M * gp.N, gp.slices, gp.N, 0, 0, 0};
     }
     int rc = fc::rg_launch(ra, s);
     if (rc != FC_OK) return rc;
     // the bias gradients: per-tile column sums in tile order (lin3.bias and res.bias see the same cotangent)
     const long bstride = H1 + H2 + Q;
-    fa.t[fa.count++] = fc::RfTask{bias_part, p->g_b1, nullptr, nullptr, H1, bstride, pl.tiles, H1, 0, 0, 1};
-    fa.t[fa.count++] = fc::RfTask{bias_part + H1, p->g_b2, nullptr, nullptr, H2, bstride, pl.tiles, H2, 0, 0, 1};
-    fa.t[fa.count++] = fc::RfTask{bias_part + H1 + H2, p->g_b3, p->g_br, nullptr, Q, bstride, pl.tiles, Q, 0, 0, 1};
+    fa.t[fa.count++] = fc::RfTask{w.bias_part, p->g_b1, nullptr, nullptr, H1, bstride, pl.tiles, H1, 0, 0, 1};
+    fa.t[fa.count++] = fc::RfTask{w.bias_part + H1, p->g_b2, nullptr, nullptr, H2, bstride, pl.tiles, H2, 0, 0, 1};
+    fa.t[fa.count++] = fc::RfTask{w.bias_part + H1 + H2, p->g_b3, p->g_br, nullptr, Q, bstride, pl.tiles, Q, 0, 0, 1};
     (void)C; (void)D;
     return fc::rf_launch(fa, s);
 }

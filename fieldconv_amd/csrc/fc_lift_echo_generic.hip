@@ -8,6 +8,7 @@
 // output entry, plain loops over edges / channels / rings, no LDS tables, no atomics, fixed summation order.  A correctness path.
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -229,8 +230,6 @@ __global__ void tfg_input_grad_kernel(const Cx<T>* __restrict__ lsten, const int
     gx[idx] = s;
 }
 
-static size_t g_align(size_t v) { return (v + 255) / 256 * 256; }
-
 template <typename T>
 static int tfg_forward(const void* x, const void* lsten, const fc_csr* t, const int64_t* perm, const void* zA, const void* zM, const void* phase,
                        void* y, void* ang, void* mag, void* s1sum, const TfgArgs& a, hipStream_t st) {
@@ -244,30 +243,32 @@ static int tfg_forward(const void* x, const void* lsten, const fc_csr* t, const 
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
+// the backward pass's workspace: the cotangents per (vertex, output, input) and per (vertex, input, ring)
+template <typename T>
+struct TfgBwdWs { Cx<T>* GA; T *GM, *GP; Cx<T>* g_ang; T* g_mag; };
+template <typename T>
+static TfgBwdWs<T> tfg_bwd_ws(Carver& c, size_t N, size_t Cin, size_t O, size_t R) {
+    const size_t noi = N * O * Cin, nir = N * Cin * R;
+    return {c.take<Cx<T>>(noi * 2 * sizeof(T)), c.take<T>(noi * sizeof(T)), c.take<T>(noi * sizeof(T)), c.take<Cx<T>>(nir * 2 * sizeof(T)),
+            c.take<T>(nir * sizeof(T))};
+}
+
 template <typename T>
 static int tfg_backward(const void* lsten, const fc_csr* s, const int64_t* perm, const void* zA, const void* zM, const void* phase,
                         const void* ang, const void* mag, const void* s1sum, const void* gy, void* gx, void* g_zA, void* g_zM, void* g_phase,
                         void* ws, const TfgArgs& a, hipStream_t st) {
     const long noi = (long)a.N * a.O * a.Cin, nir = (long)a.N * a.Cin * a.R, ni = (long)a.N * a.Cin;
-    char* w = static_cast<char*>(ws);
-    Cx<T>* GA = reinterpret_cast<Cx<T>*>(w);
-    w += g_align(noi * 2 * sizeof(T));
-    T* GM = reinterpret_cast<T*>(w);
-    w += g_align(noi * sizeof(T));
-    T* GP = reinterpret_cast<T*>(w);
-    w += g_align(noi * sizeof(T));
-    Cx<T>* g_ang = reinterpret_cast<Cx<T>*>(w);
-    w += g_align(nir * 2 * sizeof(T));
-    T* g_mag = reinterpret_cast<T*>(w);
+    Carver c(ws);
+    const TfgBwdWs<T> w = tfg_bwd_ws<T>(c, a.N, a.Cin, a.O, a.R);
     hipLaunchKernelGGL(tfg_adjoint_kernel<T>, dim3((unsigned)((noi + 255) / 256)), dim3(256), 0, st, static_cast<const Cx<T>*>(ang),
                        static_cast<const T*>(mag), static_cast<const T*>(zA), static_cast<const T*>(zM), static_cast<const T*>(phase),
-                       static_cast<const Cx<T>*>(gy), GA, GM, GP, a);
+                       static_cast<const Cx<T>*>(gy), w.GA, w.GM, w.GP, a);
     hipLaunchKernelGGL(tfg_param_grads_kernel<T>, dim3(a.O * a.Cin), dim3(256), 0, st, static_cast<const Cx<T>*>(ang),
-                       static_cast<const T*>(mag), GA, GM, GP, static_cast<T*>(g_zA), static_cast<T*>(g_zM), static_cast<T*>(g_phase), a);
-    hipLaunchKernelGGL(tfg_vertex_grads_kernel<T>, dim3((unsigned)((nir + 255) / 256)), dim3(256), 0, st, GA, GM, static_cast<const T*>(zA),
-                       static_cast<const T*>(zM), g_ang, g_mag, a);
+                       static_cast<const T*>(mag), w.GA, w.GM, w.GP, static_cast<T*>(g_zA), static_cast<T*>(g_zM), static_cast<T*>(g_phase), a);
+    hipLaunchKernelGGL(tfg_vertex_grads_kernel<T>, dim3((unsigned)((nir + 255) / 256)), dim3(256), 0, st, w.GA, w.GM, static_cast<const T*>(zA),
+                       static_cast<const T*>(zM), w.g_ang, w.g_mag, a);
     hipLaunchKernelGGL(tfg_input_grad_kernel<T>, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, static_cast<const Cx<T>*>(lsten),
-                       s->rowptr, s->nbr, perm, g_ang, g_mag, static_cast<const Cx<T>*>(s1sum), static_cast<T*>(gx), a);
+                       s->rowptr, s->nbr, perm, w.g_ang, w.g_mag, static_cast<const Cx<T>*>(s1sum), static_cast<T*>(gx), a);
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
@@ -432,9 +433,7 @@ int fc_trans_field_forward_generic(const void* x, const void* lift_sten, const f
 
 size_t fc_trans_field_backward_generic_workspace_bytes(int32_t N, int32_t Cin, int32_t O, int32_t R, int32_t dtype) {
     if (N <= 0 || Cin <= 0 || O <= 0 || R <= 0) return 0;
-    const size_t sz = dtype == FC_F64 ? 8 : 4;
-    const size_t noi = (size_t)N * O * Cin, nir = (size_t)N * Cin * R;
-    return fc::g_align(noi * 2 * sz) + 2 * fc::g_align(noi * sz) + fc::g_align(nir * 2 * sz) + fc::g_align(nir * sz);
+    return dtype == FC_F64 ? fc::carved_bytes(fc::tfg_bwd_ws<double>, N, Cin, O, R) : fc::carved_bytes(fc::tfg_bwd_ws<float>, N, Cin, O, R);
 }
 
 int fc_trans_field_backward_generic(const void* lift_sten, const fc_csr* by_source, const int64_t* slot_to_edge_s, const void* zonal_ang,
@@ -459,7 +458,7 @@ int fc_trans_field_backward_generic(const void* lift_sten, const fc_csr* by_sour
 int fc_echo_hist_dim_generic(int32_t n_bins) { return n_bins >= 1 && n_bins <= 1024 ? fc::echog_hist_dim(n_bins) : 0; }
 
 size_t fc_echo_generic_workspace_bytes(int32_t n_bins) {
-    return n_bins >= 1 && n_bins <= 1024 ? fc::g_align((size_t)(2 * n_bins + 1) * (2 * n_bins + 1) * sizeof(int)) : 0;
+    return n_bins >= 1 && n_bins <= 1024 ? fc::align256((size_t)(2 * n_bins + 1) * (2 * n_bins + 1) * sizeof(int)) : 0;
 }
 
 int fc_echo_forward_generic(const void* x, const void* ln_t, const void* wxp_t, const fc_csr* by_target, void* hist, void* desc,

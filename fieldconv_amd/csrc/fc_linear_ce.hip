@@ -18,6 +18,7 @@
 // No atomics; every sum runs in a fixed order: two runs give the same bits.  Everything lives in caller-owned buffers.
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -489,8 +490,6 @@ __global__ __launch_bounds__(256) void lc_sum_parts_kernel(const float* __restri
 
 namespace {
 
-size_t lc_round256(size_t b) { return (b + 255) / 256 * 256; }
-
 int lc_tiles(int n) { return (n + fc::kLcTile - 1) / fc::kLcTile; }
 
 // parts = 0: the most parts the library may choose when `own` tiles each own a workgroup (what the workspace query sizes for)
@@ -514,26 +513,31 @@ bool lc_parts_ok(int32_t parts) { return parts >= 0 && parts <= fc::kLcMaxParts;
 
 int lc_status() { return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH; }
 
+// The workspaces, for `p` parts: the queries lay them out for the cap on the parts when parts == 0, the entry points for the parts chosen.
+float4* lc_forward_ws(fc::Carver& c, int p, int N) { return c.take<float4>((size_t)p * N * sizeof(float4)); }       // a float4 per row and part
+
+struct LcWeightWs { float *W, *b; };                    // partials of g_W and g_b: only when there is more than one part
+LcWeightWs lc_weight_ws(fc::Carver& c, int p, int K, int H) {
+    if (p <= 1) return {nullptr, nullptr};
+    return {c.take<float>((size_t)p * K * H * sizeof(float)), c.take<float>((size_t)p * K * sizeof(float))};
+}
+
+struct LcTopkWs { float* z; int* cls; };                // k (logit, class) per row and part
+LcTopkWs lc_topk_ws(fc::Carver& c, int p, int N, int k) {
+    return {c.take<float>((size_t)p * N * k * sizeof(float)), c.take<int>((size_t)p * N * k * sizeof(int32_t))};
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t fc_linear_ce_workspace_bytes(int32_t N, int32_t H, int32_t K, int32_t parts, int32_t pass, int32_t k) {
     if (!lc_dims_ok(N, H, K) || !lc_parts_ok(parts)) return 0;
-    if (pass == 0) {                                                             /* forward: a float4 per row and part */
-        const int p = parts == 0 ? lc_parts_cap(lc_tiles(N)) : parts;
-        return lc_round256((size_t)p * N * sizeof(float4));
-    }
-    if (pass == 1) {                                                             /* backward, weight side: partials of g_W and g_b */
-        const int p = parts == 0 ? lc_parts_cap(lc_tiles(K)) : parts;
-        return p <= 1 ? 0 : lc_round256((size_t)p * K * H * sizeof(float)) + lc_round256((size_t)p * K * sizeof(float));
-    }
-    if (pass == 2) {                                                             /* top-k: k (logit, class) per row and part */
-        if (k < 1 || k > fc::kLcMaxK) return 0;
-        const int p = parts == 0 ? lc_parts_cap(lc_tiles(N)) : parts;
-        return lc_round256((size_t)p * N * k * sizeof(float)) + lc_round256((size_t)p * N * k * sizeof(int32_t));
-    }
-    return 0;
+    if (pass == 2 && (k < 1 || k > fc::kLcMaxK)) return 0;
+    const int p = parts == 0 ? lc_parts_cap(lc_tiles(pass == 1 ? K : N)) : parts;
+    if (pass == 0) return fc::carved_bytes(lc_forward_ws, p, N);
+    if (pass == 1) return fc::carved_bytes(lc_weight_ws, p, K, H);            /* backward, weight side */
+    return pass == 2 ? fc::carved_bytes(lc_topk_ws, p, N, k) : 0;
 }
 
 int fc_linear_ce_forward(const float* h, const float* weight, const float* bias, const int64_t* target, int32_t N, int32_t H, int32_t K,
@@ -544,7 +548,8 @@ int fc_linear_ce_forward(const float* h, const float* weight, const float* bias,
     if (parts == 0) parts = lc_parts_auto(lc_tiles(N), lc_tiles(K));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const fc::LcDims d{N, H, K};
-    float4* stat = static_cast<float4*>(workspace);
+    fc::Carver ws(workspace);
+    float4* stat = lc_forward_ws(ws, parts, N);
     hipLaunchKernelGGL(fc::lc_walk_kernel<0>, dim3((unsigned)lc_tiles(N), (unsigned)parts), dim3(fc::kLcThreads), 0, s, h, weight, bias, target,
                        d, parts, stat, (float*)nullptr, (int*)nullptr, 0);
     hipLaunchKernelGGL(fc::lc_finish_kernel, dim3(1), dim3(fc::kLcSumThreads), 0, s, stat, target, d, parts, (float)confidence, (float)off_value,
@@ -559,14 +564,14 @@ int fc_linear_topk(const float* h, const float* weight, const float* bias, int32
     if (parts == 0) parts = lc_parts_auto(lc_tiles(N), lc_tiles(K));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const fc::LcDims d{N, H, K};
-    float* wsZ = static_cast<float*>(workspace);
-    int* wsC = reinterpret_cast<int*>(static_cast<char*>(workspace) + lc_round256((size_t)parts * N * k * sizeof(float)));
+    fc::Carver ws(workspace);
+    const LcTopkWs w = lc_topk_ws(ws, parts, N, k);
     const dim3 grid((unsigned)lc_tiles(N), (unsigned)parts), merge((unsigned)((N + 255) / 256));
 #define FC_LC_TOPK(KL)                                                                                                                  \
     do {                                                                                                                                \
         hipLaunchKernelGGL(fc::lc_walk_kernel<KL>, grid, dim3(fc::kLcThreads), 0, s, h, weight, bias, (const int64_t*)nullptr, d, parts, \
-                           (float4*)nullptr, wsZ, wsC, k);                                                                              \
-        hipLaunchKernelGGL(fc::lc_topk_merge_kernel<KL>, merge, dim3(256), 0, s, wsZ, wsC, N, k, parts, idx, z);                        \
+                           (float4*)nullptr, w.z, w.cls, k);                                                                            \
+        hipLaunchKernelGGL(fc::lc_topk_merge_kernel<KL>, merge, dim3(256), 0, s, w.z, w.cls, N, k, parts, idx, z);                      \
     } while (0)
     if (k == 1) FC_LC_TOPK(1);
     else if (k == 2) FC_LC_TOPK(2);
@@ -601,8 +606,10 @@ int fc_linear_ce_backward_weight(const float* h, const float* weight, const floa
     float* pW = grad_weight;
     float* pb = grad_bias;
     if (parts > 1) {
-        pW = grad_weight ? static_cast<float*>(workspace) : nullptr;
-        pb = grad_bias ? reinterpret_cast<float*>(static_cast<char*>(workspace) + lc_round256((size_t)parts * nW * sizeof(float))) : nullptr;
+        fc::Carver ws(workspace);
+        const LcWeightWs w = lc_weight_ws(ws, parts, K, H);
+        pW = grad_weight ? w.W : nullptr;
+        pb = grad_bias ? w.b : nullptr;
     }
     hipLaunchKernelGGL(fc::lc_bwd_weight_kernel, dim3((unsigned)lc_tiles(K), (unsigned)parts), dim3(fc::kLcThreads), 0, s, h, weight, bias, target,
                        lse, row_scale, d, (float)confidence, (float)off_value, ignore_index, parts, pW, pb);

@@ -10,6 +10,7 @@
 // the per-workgroup partials in index order): two runs give the same bits.
 #include "../../include/fieldconv_hip.h"
 #include "fc_pair.hpp"          // d2_step / pair_d2 and the dense tile: shared with fc_match.hip
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -327,8 +328,6 @@ __global__ __launch_bounds__(kLossThreads) void label_smoothing_backward_kernel(
 
 namespace {
 
-size_t round256(size_t b) { return (b + 255) / 256 * 256; }
-
 using fc::features_ok;
 
 int launch_status() { return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH; }
@@ -442,7 +441,7 @@ int fc_pair_sqdist(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int
 
 size_t fc_twin_loss_workspace_bytes(int64_t P, int64_t M) {
     if (P < 1 || M < 1) return 0;
-    return round256((size_t)blocks_for(P + M, fc::kLossThreads) * 2 * sizeof(double));
+    return fc::align256((size_t)blocks_for(P + M, fc::kLossThreads) * 2 * sizeof(double));
 }
 
 int fc_twin_loss_forward(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int32_t C, int32_t dtype, const int64_t* p_, int64_t P,
@@ -481,7 +480,7 @@ int fc_twin_count_dense(const void* xS, int32_t N_S, const void* xT, int32_t N_T
 
 size_t fc_label_smoothing_workspace_bytes(int64_t N, int32_t K) {
     if (N < 1 || K < 1) return 0;
-    return round256((size_t)blocks_for(N, K <= 32 ? fc::kLossThreads : fc::kLossThreads / 64) * 2 * sizeof(double));
+    return fc::align256((size_t)blocks_for(N, K <= 32 ? fc::kLossThreads : fc::kLossThreads / 64) * 2 * sizeof(double));
 }
 
 int fc_label_smoothing_forward(const void* pred, const int64_t* target, const void* weight, int64_t N, int32_t K, int32_t dtype,

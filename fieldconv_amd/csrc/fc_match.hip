@@ -20,6 +20,7 @@
 // them (lower b).
 #include "../../include/fieldconv_hip.h"
 #include "fc_pair.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -234,8 +235,6 @@ __global__ __launch_bounds__(256) void match_merge_kernel(const T* __restrict__ 
 
 namespace {
 
-size_t round256(size_t b) { return (b + 255) / 256 * 256; }
-
 int tiles_of(int n) { return (n + fc::kDenseTile - 1) / fc::kDenseTile; }
 
 // parts = 0: the most parts the library may choose for N_T rows (what the workspace query sizes for)
@@ -244,29 +243,31 @@ int auto_parts_cap(int32_t nT) {
     return p < 1 ? 1 : (p > fc::kMatchMaxParts ? fc::kMatchMaxParts : p);
 }
 
-// [d2: parts N_T k entries of the dtype][idx: parts N_T k int32], each rounded up to 256 bytes; sized for 8-byte distances
-size_t match_bytes(int32_t nT, int32_t k, int parts) {
-    if (parts <= 1) return 0;          // one part writes idx / d2 itself
+// [d2: parts N_T k entries of the dtype][idx: parts N_T k int32]; the query sizes it for 8-byte distances
+template <typename T>
+struct MatchWs { T* d2; int* idx; };
+template <typename T>
+MatchWs<T> match_ws(fc::Carver& c, int32_t nT, int32_t k, int parts) {
     const size_t entries = (size_t)parts * (size_t)nT * (size_t)k;
-    return round256(entries * sizeof(double)) + round256(entries * sizeof(int32_t));
+    if (parts <= 1) return {nullptr, nullptr};          // one part writes idx / d2 itself
+    return {c.take<T>(entries * sizeof(T)), c.take<int>(entries * sizeof(int32_t))};
 }
 
 template <typename T>
 int match_topk(const void* xS, int32_t nS, const void* xT, int32_t nT, int32_t C, const int64_t* ptrS, const int64_t* ptrT, int32_t B,
                const int64_t* exclude, int32_t k, int parts, int64_t* idx, void* d2, void* ws, hipStream_t s) {
-    const size_t entries = (size_t)parts * (size_t)nT * (size_t)k;
-    T* wsD = static_cast<T*>(ws);
-    int* wsI = parts > 1 ? reinterpret_cast<int*>(static_cast<char*>(ws) + round256(entries * sizeof(T))) : nullptr;
+    fc::Carver c(ws);
+    const MatchWs<T> w = match_ws<T>(c, nT, k, parts);
     const dim3 grid((unsigned)(ptrT ? nT / fc::kDenseTile + B : tiles_of(nT)), (unsigned)parts);
 #define FC_MATCH(K)                                                                                                                      \
     do {                                                                                                                                 \
         if (parts == 1)                                                                                                                  \
             hipLaunchKernelGGL((fc::match_tile_kernel<T, K, true>), grid, dim3(fc::kDenseThreads), 0, s, static_cast<const T*>(xS), nS,  \
-                               static_cast<const T*>(xT), nT, C, ptrS, ptrT, B, exclude, k, parts, idx, static_cast<T*>(d2), wsD, wsI);  \
+                               static_cast<const T*>(xT), nT, C, ptrS, ptrT, B, exclude, k, parts, idx, static_cast<T*>(d2), w.d2, w.idx); \
         else {                                                                                                                           \
             hipLaunchKernelGGL((fc::match_tile_kernel<T, K, false>), grid, dim3(fc::kDenseThreads), 0, s, static_cast<const T*>(xS), nS, \
-                               static_cast<const T*>(xT), nT, C, ptrS, ptrT, B, exclude, k, parts, idx, static_cast<T*>(d2), wsD, wsI);  \
-            hipLaunchKernelGGL((fc::match_merge_kernel<T, K>), dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, s, wsD, wsI, nT, k,    \
+                               static_cast<const T*>(xT), nT, C, ptrS, ptrT, B, exclude, k, parts, idx, static_cast<T*>(d2), w.d2, w.idx); \
+            hipLaunchKernelGGL((fc::match_merge_kernel<T, K>), dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, s, w.d2, w.idx, nT, k, \
                                parts, idx, static_cast<T*>(d2));                                                                         \
         }                                                                                                                                \
     } while (0)
@@ -284,7 +285,7 @@ extern "C" {
 
 size_t fc_match_workspace_bytes(int32_t N_T, int32_t k, int32_t parts) {
     if (N_T < 1 || k < 1 || k > fc::kMatchMaxK || parts < 0 || parts > fc::kMatchMaxParts) return 0;
-    return match_bytes(N_T, k, parts == 0 ? auto_parts_cap(N_T) : parts);
+    return fc::carved_bytes(match_ws<double>, N_T, k, parts == 0 ? auto_parts_cap(N_T) : parts);
 }
 
 int fc_match_topk(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int32_t C, int32_t dtype, const int64_t* ptr_S,

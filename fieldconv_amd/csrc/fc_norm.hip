@@ -28,6 +28,7 @@
 // clamped to [0, N] where they are read; a row that a malformed ptr leaves in no mesh is written as zero.
 #include "../../include/fieldconv_hip.h"
 #include "fc_segment.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -163,31 +164,26 @@ __global__ void norm_gain_kernel(const T* __restrict__ rr, const T* __restrict__
 
 namespace {
 
-using fc::seg_round256;
 using fc::seg_slots;
 
 bool norm_dims_ok(int32_t N, int32_t B, int32_t C, int32_t dtype) { return fc::seg_shape_ok(N, B, C) && (dtype == FC_F32 || dtype == FC_F64); }
 
 // workspace: partial (slots, C) | wsum (slots) | t (B, C) | W (B), each rounded up to 256 bytes; the forward pass uses the first two
-struct NormWorkspace {
-    size_t partial, wsum, t, wtot, total;
-    NormWorkspace(int32_t N, int32_t B, int32_t C, size_t item) {
-        const size_t slots = (size_t)seg_slots(N, B);
-        partial = 0;
-        wsum = partial + seg_round256(slots * (size_t)C * item);
-        t = wsum + seg_round256(slots * item);
-        wtot = t + seg_round256((size_t)B * (size_t)C * item);
-        total = wtot + seg_round256((size_t)B * item);
-    }
-};
+template <typename T>
+struct NormWorkspace { T *partial, *wsum, *t, *wtot; };
+template <typename T>
+NormWorkspace<T> norm_workspace(fc::Carver& c, int32_t N, int32_t B, int32_t C) {
+    const size_t slots = (size_t)seg_slots(N, B);
+    return {c.take<T>(slots * (size_t)C * sizeof(T)), c.take<T>(slots * sizeof(T)), c.take<T>((size_t)B * (size_t)C * sizeof(T)),
+            c.take<T>((size_t)B * sizeof(T))};
+}
 
 template <typename T>
 int norm_forward(const void* x, const void* w, const int64_t* ptr, const void* gain, int32_t N, int32_t B, int32_t C, double eps, void* y,
                  void* r, void* workspace, hipStream_t s) {
-    const NormWorkspace ws(N, B, C, sizeof(T));
-    char* base = static_cast<char*>(workspace);
-    T* partial = reinterpret_cast<T*>(base + ws.partial);
-    T* wsum = w ? reinterpret_cast<T*>(base + ws.wsum) : nullptr;
+    fc::Carver c(workspace);
+    const NormWorkspace<T> ws = norm_workspace<T>(c, N, B, C);
+    T *partial = ws.partial, *wsum = w ? ws.wsum : nullptr;             // (wsum takes room whether or not there are weights)
     const auto* xc = static_cast<const fc::SegCx<T>*>(x);
     const T* wt = static_cast<const T*>(w);
     const dim3 block(fc::kSegThreads);
@@ -206,12 +202,9 @@ int norm_forward(const void* x, const void* w, const int64_t* ptr, const void* g
 template <typename T>
 int norm_backward(const void* x, const void* w, const int64_t* ptr, const void* gain, const void* r, const void* gy, int32_t N, int32_t B,
                   int32_t C, void* gx, void* ggain, void* workspace, hipStream_t s) {
-    const NormWorkspace ws(N, B, C, sizeof(T));
-    char* base = static_cast<char*>(workspace);
-    T* partial = reinterpret_cast<T*>(base + ws.partial);
-    T* wsum = w ? reinterpret_cast<T*>(base + ws.wsum) : nullptr;
-    T* t = reinterpret_cast<T*>(base + ws.t);
-    T* wtot = reinterpret_cast<T*>(base + ws.wtot);
+    fc::Carver c(workspace);
+    const NormWorkspace<T> ws = norm_workspace<T>(c, N, B, C);
+    T *partial = ws.partial, *wsum = w ? ws.wsum : nullptr, *t = ws.t, *wtot = ws.wtot;
     const auto* xc = static_cast<const fc::SegCx<T>*>(x);
     const auto* gc = static_cast<const fc::SegCx<T>*>(gy);
     const T* wt = static_cast<const T*>(w);
@@ -235,7 +228,7 @@ extern "C" {
 
 size_t fc_tangent_norm_workspace_bytes(int32_t N, int32_t B, int32_t C, int32_t dtype) {
     if (!norm_dims_ok(N, B, C, dtype)) return 0;
-    return NormWorkspace(N, B, C, dtype == FC_F64 ? 8 : 4).total;
+    return dtype == FC_F64 ? fc::carved_bytes(norm_workspace<double>, N, B, C) : fc::carved_bytes(norm_workspace<float>, N, B, C);
 }
 
 int fc_tangent_norm_forward(const void* x, const void* w, const int64_t* ptr, const void* gain, int32_t N, int32_t B, int32_t C, int32_t dtype,

@@ -11,6 +11,7 @@
 #include <hipcub/hipcub.hpp>
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -103,17 +104,13 @@ int precomp_area_sums(const int64_t* edges, const int32_t* keep, const float* w,
 
 }  // namespace fc
 
-// keep | pos, each (E+2) int32 rounded up to 256 bytes: pos[E] = number of kept edges, pos[E+1] = index-range flag
-static size_t precomp_seg(int32_t E) { return ((size_t)(E + 2) * 4 + 255) / 256 * 256; }
-
 extern "C" {
 
 size_t fc_precomp_workspace_bytes(int32_t N, int32_t E) {
     if (N <= 0 || E < 0) return 0;
     size_t scan = 0;
     hipcub::DeviceScan::ExclusiveSum(nullptr, scan, (const int32_t*)nullptr, (int32_t*)nullptr, E + 1);
-    // keep | pos | total (N) | scan scratch
-    return precomp_seg(E) * 2 + ((size_t)N * 4 + 255) / 256 * 256 + scan + 256;
+    return fc::carved_bytes(fc::precomp_selection, N, E) + scan + 256;             // the scan's scratch (its size as hipcub states it) and slack lie behind the selection
 }
 
 // Step 1: marks the edges inside the support radius and scans them; afterwards the two int32 at
@@ -124,11 +121,10 @@ int fc_precomp_mark(const float* log_mag, const int64_t* supp_edges, float epsil
     if (!log_mag || !workspace || N <= 0 || E < 0 || !(epsilon > 0.f)) return FC_ERR_BAD_ARGUMENT;
     if (workspace_bytes < fc_precomp_workspace_bytes(N, E)) return FC_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t seg = precomp_seg(E);
-    char* w = static_cast<char*>(workspace);
-    int32_t* keep = reinterpret_cast<int32_t*>(w);
-    int32_t* pos = reinterpret_cast<int32_t*>(w + seg);
-    void* scan = w + 2 * seg + ((size_t)N * 4 + 255) / 256 * 256;
+    fc::Carver c(workspace);
+    const fc::PrecompSelection sel = fc::precomp_selection(c, N, E);
+    int32_t *keep = sel.keep, *pos = sel.pos;
+    void* scan = c.base + c.used;           // behind the selection
     size_t scan_bytes = 0;
     hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, keep, pos, E + 1);
     if (hipMemsetAsync(pos + E + 1, 0, 4, s) != hipSuccess) return FC_ERR_LAUNCH;
@@ -139,7 +135,8 @@ int fc_precomp_mark(const float* log_mag, const int64_t* supp_edges, float epsil
 }
 
 const int32_t* fc_precomp_kept_count_ptr(const void* workspace, int32_t E) {
-    return reinterpret_cast<const int32_t*>(static_cast<const char*>(workspace) + precomp_seg(E)) + E;
+    fc::Carver c(workspace);
+    return fc::precomp_selection(c, 0, E).pos + E;            // (pos lies where E alone puts it: total, the piece N sizes, comes last)
 }
 
 // Step 2: outputs sized for the E' kept edges: supp_edges_out (E',2) int64, supp_sten (E',R,F) c64, ln (E') c64, wxp (E') c64.
@@ -152,11 +149,10 @@ int fc_precomp_build(const float* log_mag, const float* log_ang, const float* xp
     if (E == 0) return FC_OK;
     if (!supp_edges_out || !supp_sten || !ln || !wxp) return FC_ERR_BAD_ARGUMENT;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t seg = precomp_seg(E);
-    char* wsp = static_cast<char*>(workspace);
-    const int32_t* keep = reinterpret_cast<const int32_t*>(wsp);
-    const int32_t* pos = reinterpret_cast<const int32_t*>(wsp + seg);
-    float* total = reinterpret_cast<float*>(wsp + 2 * seg);
+    fc::Carver c(workspace);
+    const fc::PrecompSelection sel = fc::precomp_selection(c, N, E);
+    const int32_t *keep = sel.keep, *pos = sel.pos;
+    float* total = sel.total;
     if (fc::precomp_area_sums(supp_edges, keep, w, total, N, E, s) != FC_OK) return FC_ERR_LAUNCH;
     static bool lds_ok[fc::kMaxDevices] = {};
     if (!fc::allow_full_lds(reinterpret_cast<const void*>(fc::precomp_stencil_kernel), (size_t)fc::kPrecompEdges * R * F * sizeof(float2), lds_ok))

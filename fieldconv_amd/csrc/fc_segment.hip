@@ -23,6 +23,7 @@
 // the buffers.
 #include "../../include/fieldconv_hip.h"
 #include "fc_segment.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -121,7 +122,6 @@ __global__ __launch_bounds__(kSegThreads) void segment_backward_kernel(const voi
 
 namespace {
 
-using fc::seg_round256;
 using fc::seg_slots;
 
 bool seg_dims_ok(int32_t N, int32_t B, int32_t C, int32_t dtype, int32_t reduce) {
@@ -156,7 +156,7 @@ extern "C" {
 
 size_t fc_segment_pool_workspace_bytes(int32_t N, int32_t B, int32_t C, int32_t dtype) {
     if (!seg_dims_ok(N, B, C, dtype, 0)) return 0;
-    return seg_round256((size_t)seg_slots(N, B) * (size_t)C * (dtype == FC_F64 ? 8 : 4));
+    return fc::align256((size_t)seg_slots(N, B) * (size_t)C * (dtype == FC_F64 ? 8 : 4));
 }
 
 int fc_segment_pool_soft_abs_forward(const void* x, const int64_t* ptr, int32_t N, int32_t B, int32_t C, int32_t dtype, int32_t reduce,

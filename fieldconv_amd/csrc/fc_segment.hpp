@@ -61,8 +61,6 @@ template <typename T> __device__ __forceinline__ T seg_combine(T (*acc)[64], T s
     return (acc[0][lane] + acc[1][lane]) + (acc[2][lane] + acc[3][lane]);
 }
 
-inline size_t seg_round256(size_t b) { return (b + 255) / 256 * 256; }
-
 // the channel tiles are the grid's y extent; N + 64 B stays within 32 bits so that no slot or row index overflows
 inline bool seg_shape_ok(int32_t N, int32_t B, int32_t C) {
     return N >= 0 && B >= 1 && C >= 1 && C <= 64 * 65535 && (int64_t)N + 64 * (int64_t)B < 2147483647LL;

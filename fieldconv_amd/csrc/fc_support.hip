@@ -10,6 +10,7 @@
 #include <hipcub/hipcub.hpp>
 #include "../../include/fieldconv_hip.h"
 #include "fc_common.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
@@ -307,24 +308,22 @@ __global__ __launch_bounds__(kRadiusThreads) void radius_fill_batched_kernel(con
 
 namespace {
 
-size_t round256(size_t b) { return (b + 255) / 256 * 256; }
-
 // radius workspace: count (N+1) int64 | offsets (N+1) int64 | overfull (N) int32 | thresh (N) uint32 | quota (N) int32 | scan scratch
-struct RadiusLayout {
-    size_t count, offsets, overfull, thresh, quota, scan, scan_bytes, total;
-    explicit RadiusLayout(int32_t N) {
-        const size_t n = (size_t)N;
-        count = 0;
-        offsets = count + round256((n + 1) * 8);
-        overfull = offsets + round256((n + 1) * 8);
-        thresh = overfull + round256(n * 4);
-        quota = thresh + round256(n * 4);
-        scan = quota + round256(n * 4);
-        scan_bytes = 0;
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)nullptr, (int64_t*)nullptr, N + 1);
-        total = scan + round256(scan_bytes);
-    }
-};
+struct RadiusWs { int64_t *count, *offsets; int32_t* overfull; uint32_t* thresh; int32_t* quota; void* scan; size_t scan_bytes; };
+RadiusWs radius_ws(fc::Carver& c, int32_t N) {
+    const size_t n = (size_t)N;
+    RadiusWs w;
+    w.count = c.take<int64_t>((n + 1) * 8);
+    w.offsets = c.take<int64_t>((n + 1) * 8);
+    w.overfull = c.take<int32_t>(n * 4);
+    w.thresh = c.take<uint32_t>(n * 4);
+    w.quota = c.take<int32_t>(n * 4);
+    w.scan_bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, w.scan_bytes, (const int64_t*)nullptr, (int64_t*)nullptr, N + 1);
+    w.scan = c.take(w.scan_bytes);
+    return w;
+}
+size_t radius_bytes(int32_t N) { return fc::carved_bytes(radius_ws, N); }
 
 bool finite_positive(float x) { return x > 0.f && x <= 3.402823466e38f; }
 
@@ -334,7 +333,7 @@ extern "C" {
 
 size_t fc_fps_workspace_bytes(int32_t N) {
     if (N < 1) return 0;
-    return round256((size_t)N * 4);
+    return fc::align256((size_t)N * 4);
 }
 
 int fc_fps(const float* pos, int32_t N, int32_t n_samples, int32_t start, int64_t* idx, void* workspace, size_t workspace_bytes,
@@ -348,47 +347,43 @@ int fc_fps(const float* pos, int32_t N, int32_t n_samples, int32_t start, int64_
 
 size_t fc_radius_workspace_bytes(int32_t N) {
     if (N < 1) return 0;
-    return RadiusLayout(N).total;
+    return radius_bytes(N);
 }
 
 int fc_radius_count(const float* pos, int32_t N, float epsilon, int32_t max_num_neighbors, void* workspace, size_t workspace_bytes,
                     void* stream) {
     if (!pos || !workspace || N < 1 || !finite_positive(epsilon) || max_num_neighbors < 1) return FC_ERR_BAD_ARGUMENT;
-    const RadiusLayout L(N);
-    if (workspace_bytes < L.total) return FC_ERR_WORKSPACE;
+    if (workspace_bytes < radius_bytes(N)) return FC_ERR_WORKSPACE;
+    fc::Carver ws(workspace);
+    const RadiusWs L = radius_ws(ws, N);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace);
-    int64_t* count = reinterpret_cast<int64_t*>(w + L.count);
-    int64_t* offsets = reinterpret_cast<int64_t*>(w + L.offsets);
-    int32_t* overfull = reinterpret_cast<int32_t*>(w + L.overfull);
     const float r2 = epsilon * epsilon;
     const int K = max_num_neighbors;
     hipLaunchKernelGGL(fc::radius_count_kernel, dim3(N / fc::kRadiusThreads + 1), dim3(fc::kRadiusThreads), 0, s, pos, N, r2, K,
-                       count, overfull);
-    hipLaunchKernelGGL(fc::radius_select_kernel, dim3((N + 3) / 4), dim3(256), 0, s, pos, N, r2, K, overfull,
-                       reinterpret_cast<uint32_t*>(w + L.thresh), reinterpret_cast<int32_t*>(w + L.quota));
+                       L.count, L.overfull);
+    hipLaunchKernelGGL(fc::radius_select_kernel, dim3((N + 3) / 4), dim3(256), 0, s, pos, N, r2, K, L.overfull,
+                       L.thresh, L.quota);
     size_t scan_bytes = L.scan_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum(w + L.scan, scan_bytes, count, offsets, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
+    if (hipcub::DeviceScan::ExclusiveSum(L.scan, scan_bytes, L.count, L.offsets, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
 const int64_t* fc_radius_edge_count_ptr(const void* workspace, int32_t N) {
     if (!workspace || N < 1) return nullptr;
-    return reinterpret_cast<const int64_t*>(static_cast<const char*>(workspace) + RadiusLayout(N).offsets) + N;
+    fc::Carver ws(workspace);
+    return radius_ws(ws, N).offsets + N;
 }
 
 int fc_radius_fill(const float* pos, int32_t N, float epsilon, int32_t max_num_neighbors, int64_t E, int64_t* supp_edges,
                    void* workspace, size_t workspace_bytes, void* stream) {
     if (!pos || !workspace || N < 1 || !finite_positive(epsilon) || max_num_neighbors < 1 || E < 0) return FC_ERR_BAD_ARGUMENT;
     if (E > 0 && !supp_edges) return FC_ERR_BAD_ARGUMENT;
-    const RadiusLayout L(N);
-    if (workspace_bytes < L.total) return FC_ERR_WORKSPACE;
+    if (workspace_bytes < radius_bytes(N)) return FC_ERR_WORKSPACE;
+    fc::Carver ws(workspace);
+    const RadiusWs L = radius_ws(ws, N);
     if (E == 0) return FC_OK;
-    char* w = static_cast<char*>(workspace);
     hipLaunchKernelGGL(fc::radius_fill_kernel, dim3((N + fc::kRadiusThreads - 1) / fc::kRadiusThreads), dim3(fc::kRadiusThreads), 0,
-                       static_cast<hipStream_t>(stream), pos, N, epsilon * epsilon, E, reinterpret_cast<const int64_t*>(w + L.offsets),
-                       reinterpret_cast<const int32_t*>(w + L.overfull), reinterpret_cast<const uint32_t*>(w + L.thresh),
-                       reinterpret_cast<const int32_t*>(w + L.quota), supp_edges);
+                       static_cast<hipStream_t>(stream), pos, N, epsilon * epsilon, E, L.offsets, L.overfull, L.thresh, L.quota, supp_edges);
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
@@ -409,24 +404,21 @@ int fc_radius_count_batched(const float* pos, const int64_t* ptr, int32_t N, int
     if (!pos || !ptr || !workspace || N < 1 || B < 1 || !finite_positive(epsilon) || max_num_neighbors < 1 ||
         (int64_t)N + (int64_t)fc::kRadiusThreads * B >= 2147483647LL)
         return FC_ERR_BAD_ARGUMENT;
-    const RadiusLayout L(N);
-    if (workspace_bytes < L.total) return FC_ERR_WORKSPACE;
+    if (workspace_bytes < radius_bytes(N)) return FC_ERR_WORKSPACE;
+    fc::Carver ws(workspace);
+    const RadiusWs L = radius_ws(ws, N);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace);
-    int64_t* count = reinterpret_cast<int64_t*>(w + L.count);
-    int64_t* offsets = reinterpret_cast<int64_t*>(w + L.offsets);
-    int32_t* overfull = reinterpret_cast<int32_t*>(w + L.overfull);
     const float r2 = epsilon * epsilon;
     const int K = max_num_neighbors;
     // a query that no (mesh, tile) pair covers (a malformed ptr) counts nothing
-    if (hipMemsetAsync(count, 0, (size_t)N * 8, s) != hipSuccess || hipMemsetAsync(overfull, 0, (size_t)N * 4, s) != hipSuccess)
+    if (hipMemsetAsync(L.count, 0, (size_t)N * 8, s) != hipSuccess || hipMemsetAsync(L.overfull, 0, (size_t)N * 4, s) != hipSuccess)
         return FC_ERR_LAUNCH;
     hipLaunchKernelGGL(fc::radius_count_batched_kernel, dim3((unsigned)(N / fc::kRadiusThreads + B)), dim3(fc::kRadiusThreads), 0, s, pos,
-                       ptr, B, N, r2, K, count, overfull);
-    hipLaunchKernelGGL(fc::radius_select_batched_kernel, dim3((N + 3) / 4), dim3(256), 0, s, pos, ptr, B, N, r2, K, overfull,
-                       reinterpret_cast<uint32_t*>(w + L.thresh), reinterpret_cast<int32_t*>(w + L.quota));
+                       ptr, B, N, r2, K, L.count, L.overfull);
+    hipLaunchKernelGGL(fc::radius_select_batched_kernel, dim3((N + 3) / 4), dim3(256), 0, s, pos, ptr, B, N, r2, K, L.overfull,
+                       L.thresh, L.quota);
     size_t scan_bytes = L.scan_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum(w + L.scan, scan_bytes, count, offsets, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
+    if (hipcub::DeviceScan::ExclusiveSum(L.scan, scan_bytes, L.count, L.offsets, N + 1, s) != hipSuccess) return FC_ERR_LAUNCH;
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
@@ -436,14 +428,12 @@ int fc_radius_fill_batched(const float* pos, const int64_t* ptr, int32_t N, int3
         (int64_t)N + (int64_t)fc::kRadiusThreads * B >= 2147483647LL)
         return FC_ERR_BAD_ARGUMENT;
     if (E > 0 && !supp_edges) return FC_ERR_BAD_ARGUMENT;
-    const RadiusLayout L(N);
-    if (workspace_bytes < L.total) return FC_ERR_WORKSPACE;
+    if (workspace_bytes < radius_bytes(N)) return FC_ERR_WORKSPACE;
+    fc::Carver ws(workspace);
+    const RadiusWs L = radius_ws(ws, N);
     if (E == 0) return FC_OK;
-    char* w = static_cast<char*>(workspace);
     hipLaunchKernelGGL(fc::radius_fill_batched_kernel, dim3((unsigned)(N / fc::kRadiusThreads + B)), dim3(fc::kRadiusThreads), 0,
-                       static_cast<hipStream_t>(stream), pos, ptr, B, N, epsilon * epsilon, E, reinterpret_cast<const int64_t*>(w + L.offsets),
-                       reinterpret_cast<const int32_t*>(w + L.overfull), reinterpret_cast<const uint32_t*>(w + L.thresh),
-                       reinterpret_cast<const int32_t*>(w + L.quota), supp_edges);
+                       static_cast<hipStream_t>(stream), pos, ptr, B, N, epsilon * epsilon, E, L.offsets, L.overfull, L.thresh, L.quota, supp_edges);
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 

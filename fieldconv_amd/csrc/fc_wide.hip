@@ -13,16 +13,15 @@
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
 #include "fc_tile.hpp"
+#include "fc_workspace.hpp"
 
 namespace fc {
 
 struct WidePlan {
     int blk, nib, nob;
     fc_dims db;                    // dims of a full block (I = O = blk)
-    size_t x_blocks, y_block, gy_blocks, gx_parts, gx_block, wpk, gw_block, conv_ws, total_fwd, total_bwd;
+    int records;
 };
-
-static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 static bool wide_plan(const fc_dims* d, int blk, int records, WidePlan& p) {
     if (blk <= 0 || blk > kMaxChannels) return false;
@@ -32,20 +31,39 @@ static bool wide_plan(const fc_dims* d, int blk, int records, WidePlan& p) {
     p.db = *d;
     p.db.I = blk;
     p.db.O = blk;
-    const size_t rows = (size_t)d->N;
-    p.x_blocks = align256(rows * p.nib * blk * 8);          // x cut into contiguous (N, blk) blocks (the last one narrower)
-    p.y_block = align256(rows * blk * 8);
-    p.gy_blocks = align256(rows * p.nob * blk * 8);
-    p.gx_parts = align256(rows * blk * 8) * p.nob;         // one partial input-gradient block per output block
-    p.gx_block = align256(rows * blk * 8);
-    const size_t wf = packed_filter_floats_fwd(&p.db, records), wb = packed_filter_floats_bwd(&p.db, records);
-    p.wpk = align256((wf > wb ? wf : wb) * sizeof(float));
-    p.gw_block = align256((size_t)blk * blk * d->R * (2 * d->B + 1) * 8);
-    const size_t fws = records ? forward_workspace_bytes(&p.db, 1) : 0, bws = backward_workspace_bytes(&p.db);
-    p.conv_ws = align256(fws > bws ? fws : bws);
-    p.total_fwd = p.x_blocks + p.y_block + p.wpk + align256(fws);
-    p.total_bwd = p.x_blocks + p.gy_blocks + p.gx_parts + p.gx_block + p.wpk + p.gw_block + align256(bws);
+    p.records = records;
     return true;
+}
+
+static size_t wide_wpk_bytes(const WidePlan& p) {          // one image at a time: the forward one or the backward one
+    const size_t wf = packed_filter_floats_fwd(&p.db, p.records), wb = packed_filter_floats_bwd(&p.db, p.records);
+    return (wf > wb ? wf : wb) * sizeof(float);
+}
+
+struct WideFwdWs { float *xb, *yb, *wpk; void* cws; size_t cws_bytes; };
+static WideFwdWs wide_fwd_ws(Carver& c, const WidePlan& p) {
+    const size_t rows = (size_t)p.db.N;
+    WideFwdWs w;
+    w.xb = c.take<float>(rows * p.nib * p.blk * 8);          // x cut into contiguous (N, blk) blocks (the last one narrower)
+    w.yb = c.take<float>(rows * p.blk * 8);
+    w.wpk = c.take<float>(wide_wpk_bytes(p));
+    w.cws = c.take(p.records ? forward_workspace_bytes(&p.db, 1) : 0, &w.cws_bytes);
+    return w;
+}
+
+struct WideBwdWs { float *xb, *gyb, *parts, *gxb, *wpk, *gwb; void* cws; size_t pstride, cws_bytes; };
+static WideBwdWs wide_bwd_ws(Carver& c, const WidePlan& p) {
+    const size_t rows = (size_t)p.db.N;
+    WideBwdWs w;
+    w.xb = c.take<float>(rows * p.nib * p.blk * 8);
+    w.gyb = c.take<float>(rows * p.nob * p.blk * 8);
+    w.pstride = align256(rows * p.blk * 8) / sizeof(float);
+    w.parts = c.take<float>(w.pstride * sizeof(float) * p.nob);         // one partial input-gradient block per output block, pstride floats apart
+    w.gxb = c.take<float>(rows * p.blk * 8);
+    w.wpk = c.take<float>(wide_wpk_bytes(p));
+    w.gwb = c.take<float>((size_t)p.blk * p.blk * p.db.R * (2 * p.db.B + 1) * 8);
+    w.cws = c.take(backward_workspace_bytes(&p.db), &w.cws_bytes);
+    return w;
 }
 
 // (rows, cols) complex numbers from a matrix with `ld_src` columns per row to one with `ld_dst`
@@ -64,7 +82,7 @@ extern "C" {
 size_t fc_wide_workspace_bytes(const fc_dims* dims, int32_t block, int32_t records, int32_t backward) {
     fc::WidePlan p;
     if (!dims || dims->N <= 0 || dims->I <= 0 || dims->O <= 0 || !fc::wide_plan(dims, block, records, p)) return 0;
-    return backward ? p.total_bwd : p.total_fwd;
+    return backward ? fc::carved_bytes(fc::wide_bwd_ws, p) : fc::carved_bytes(fc::wide_fwd_ws, p);
 }
 
 int fc_forward_wide(const float* x, const float* sten_or_records, const fc_csr* by_target, int32_t kind, const fc_filter_params* params,
@@ -77,19 +95,15 @@ int fc_forward_wide(const float* x, const float* sten_or_records, const fc_csr* 
     if (!fc_supported(&p.db)) return FC_ERR_UNSUPPORTED;
     if (!by_target->rowptr || (dims->E > 0 && (!sten_or_records || (records ? !by_target->runs : !by_target->nbr)))) return FC_ERR_BAD_ARGUMENT;
     if (records && (dims->R > 8 || !fc::rows_fit_32bit(&p.db))) return FC_ERR_UNSUPPORTED;          // the guards of the per-block entry points
-    if (!workspace || workspace_bytes < p.total_fwd) return FC_ERR_WORKSPACE;
+    if (!workspace || workspace_bytes < fc::carved_bytes(fc::wide_fwd_ws, p)) return FC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace);
-    float* xb = reinterpret_cast<float*>(w);
-    float* yb = reinterpret_cast<float*>(w + p.x_blocks);
-    float* wpk = reinterpret_cast<float*>(w + p.x_blocks + p.y_block);
-    void* cws = w + p.x_blocks + p.y_block + p.wpk;
-    const size_t cws_bytes = p.total_fwd - (p.x_blocks + p.y_block + p.wpk);
+    fc::Carver ws(workspace);
+    const fc::WideFwdWs w = fc::wide_fwd_ws(ws, p);
     const int N = dims->N, I = dims->I, O = dims->O, blk = p.blk;
     const size_t xstride = (size_t)N * blk * 2;              // floats between the x blocks
     for (int ib = 0; ib < p.nib; ++ib) {
         const int bi = (I - ib * blk) < blk ? (I - ib * blk) : blk;
-        const int rc = fc::copy_block(xb + ib * xstride, bi, x + 2 * (size_t)ib * blk, I, N, bi, st);
+        const int rc = fc::copy_block(w.xb + ib * xstride, bi, x + 2 * (size_t)ib * blk, I, N, bi, st);
         if (rc != FC_OK) return rc;
     }
     for (int ob = 0; ob < p.nob; ++ob) {
@@ -99,17 +113,17 @@ int fc_forward_wide(const float* x, const float* sten_or_records, const fc_csr* 
             fc_dims d = *dims;
             d.I = bi;
             d.O = bo;
-            int rc = params ? fc::pack_filter_params_block_impl(params->zonal, params->spherical, params->phase, params->ftype, wpk, nullptr, &d,
+            int rc = params ? fc::pack_filter_params_block_impl(params->zonal, params->spherical, params->phase, params->ftype, w.wpk, nullptr, &d,
                                                                 records, ob * blk, ib * blk, I, st)
-                            : fc::pack_filter_block_impl(w_eff, wpk, nullptr, &d, records, ob * blk, ib * blk, I, st);
+                            : fc::pack_filter_block_impl(w_eff, w.wpk, nullptr, &d, records, ob * blk, ib * blk, I, st);
             if (rc != FC_OK) return rc;
-            fc_epilogue epi = {ib > 0 ? yb : nullptr, nullptr, nullptr};      // the sum over the input blocks: y_block += this block's output
+            fc_epilogue epi = {ib > 0 ? w.yb : nullptr, nullptr, nullptr};      // the sum over the input blocks: y_block += this block's output
             const size_t fws = records ? fc::forward_workspace_bytes(&d, kind) : 0;
-            rc = fc::forward_impl(xb + ib * xstride, sten_or_records, by_target, wpk, yb, &d, kind, fws && fws <= cws_bytes ? cws : nullptr,
-                                  fws && fws <= cws_bytes ? fws : 0, ib > 0 ? &epi : nullptr, st);
+            rc = fc::forward_impl(w.xb + ib * xstride, sten_or_records, by_target, w.wpk, w.yb, &d, kind, fws && fws <= w.cws_bytes ? w.cws : nullptr,
+                                  fws && fws <= w.cws_bytes ? fws : 0, ib > 0 ? &epi : nullptr, st);
             if (rc != FC_OK) return rc;
         }
-        const int rc = fc::copy_block(y + 2 * (size_t)ob * blk, O, yb, bo, N, bo, st);
+        const int rc = fc::copy_block(y + 2 * (size_t)ob * blk, O, w.yb, bo, N, bo, st);
         if (rc != FC_OK) return rc;
     }
     return FC_OK;
@@ -125,28 +139,20 @@ int fc_backward_wide(const float* x, const float* gy, const float* sten_or_rec_s
     if (!fc_supported(&p.db)) return FC_ERR_UNSUPPORTED;
     if (!by_source->rowptr || (dims->E > 0 && (!sten_or_rec_s || (records ? !by_source->runs : !by_source->nbr)))) return FC_ERR_BAD_ARGUMENT;
     if (records && (dims->R > 8 || !fc::rows_fit_32bit(&p.db))) return FC_ERR_UNSUPPORTED;          // the guards of the per-block entry points
-    if (!workspace || workspace_bytes < p.total_bwd) return FC_ERR_WORKSPACE;
+    if (!workspace || workspace_bytes < fc::carved_bytes(fc::wide_bwd_ws, p)) return FC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace);
-    float* xb = reinterpret_cast<float*>(w);
-    float* gyb = reinterpret_cast<float*>(w + p.x_blocks);
-    float* parts = reinterpret_cast<float*>(w + p.x_blocks + p.gy_blocks);
-    float* gxb = reinterpret_cast<float*>(w + p.x_blocks + p.gy_blocks + p.gx_parts);
-    float* wpk = reinterpret_cast<float*>(w + p.x_blocks + p.gy_blocks + p.gx_parts + p.gx_block);
-    float* gwb = reinterpret_cast<float*>(w + p.x_blocks + p.gy_blocks + p.gx_parts + p.gx_block + p.wpk);
-    void* cws = w + p.x_blocks + p.gy_blocks + p.gx_parts + p.gx_block + p.wpk + p.gw_block;
-    const size_t cws_bytes = p.total_bwd - (p.x_blocks + p.gy_blocks + p.gx_parts + p.gx_block + p.wpk + p.gw_block);
+    fc::Carver ws(workspace);
+    const fc::WideBwdWs w = fc::wide_bwd_ws(ws, p);
     const int N = dims->N, I = dims->I, O = dims->O, blk = p.blk;
     const size_t bstride = (size_t)N * blk * 2;              // floats between the x / gy blocks
-    const size_t pstride = p.gx_parts / p.nob / sizeof(float);
     for (int ib = 0; ib < p.nib; ++ib) {
         const int bi = (I - ib * blk) < blk ? (I - ib * blk) : blk;
-        const int rc = fc::copy_block(xb + ib * bstride, bi, x + 2 * (size_t)ib * blk, I, N, bi, st);
+        const int rc = fc::copy_block(w.xb + ib * bstride, bi, x + 2 * (size_t)ib * blk, I, N, bi, st);
         if (rc != FC_OK) return rc;
     }
     for (int ob = 0; ob < p.nob; ++ob) {
         const int bo = (O - ob * blk) < blk ? (O - ob * blk) : blk;
-        const int rc = fc::copy_block(gyb + ob * bstride, bo, gy + 2 * (size_t)ob * blk, O, N, bo, st);
+        const int rc = fc::copy_block(w.gyb + ob * bstride, bo, gy + 2 * (size_t)ob * blk, O, N, bo, st);
         if (rc != FC_OK) return rc;
     }
     for (int ib = 0; ib < p.nib; ++ib) {
@@ -156,35 +162,35 @@ int fc_backward_wide(const float* x, const float* gy, const float* sten_or_rec_s
             fc_dims d = *dims;
             d.I = bi;
             d.O = bo;
-            int rc = params ? fc::pack_filter_params_block_impl(params->zonal, params->spherical, params->phase, params->ftype, nullptr, wpk, &d,
+            int rc = params ? fc::pack_filter_params_block_impl(params->zonal, params->spherical, params->phase, params->ftype, nullptr, w.wpk, &d,
                                                                 records, ob * blk, ib * blk, I, st)
-                            : fc::pack_filter_block_impl(w_eff, nullptr, wpk, &d, records, ob * blk, ib * blk, I, st);
+                            : fc::pack_filter_block_impl(w_eff, nullptr, w.wpk, &d, records, ob * blk, ib * blk, I, st);
             if (rc != FC_OK) return rc;
-            float* part = p.nob == 1 ? gxb : parts + ob * pstride;
-            rc = fc::backward_data_impl(xb + ib * bstride, gyb + ob * bstride, sten_or_rec_s, by_source, wpk, part, cws, cws_bytes, &d, records != 0,
+            float* part = p.nob == 1 ? w.gxb : w.parts + ob * w.pstride;
+            rc = fc::backward_data_impl(w.xb + ib * bstride, w.gyb + ob * bstride, sten_or_rec_s, by_source, w.wpk, part, w.cws, w.cws_bytes, &d, records != 0,
                                         st);
             if (rc != FC_OK) return rc;
-            rc = fc::backward_filter_impl(xb + ib * bstride, cws, cws_bytes, &d, st, records != 0);
+            rc = fc::backward_filter_impl(w.xb + ib * bstride, w.cws, w.cws_bytes, &d, st, records != 0);
             if (rc != FC_OK) return rc;
             if (params) {
                 fc_filter_params block_params = *params;             // (the bias rider belongs to the whole layer: after the blocks)
                 block_params.bias_partials = nullptr;
                 block_params.bias_nparts = 0;
                 block_params.g_bias = nullptr;
-                rc = fc::backward_finish_params_impl(gwb, cws, cws_bytes, &d, &block_params, st, ob * blk, ib * blk, I, nullptr, records != 0);
+                rc = fc::backward_finish_params_impl(w.gwb, w.cws, w.cws_bytes, &d, &block_params, st, ob * blk, ib * blk, I, nullptr, records != 0);
             } else {            // explicit filter: the block's gradient goes into its block of gw_eff (rows o, bi*R*F numbers each)
-                rc = fc::backward_finish_impl(gwb, cws, cws_bytes, &d, st, records != 0);
+                rc = fc::backward_finish_impl(w.gwb, w.cws, w.cws_bytes, &d, st, records != 0);
                 const int rf = dims->R * (2 * dims->B + 1);
                 if (rc == FC_OK)
-                    rc = fc::copy_block(gw_eff + 2 * (((size_t)ob * blk * I + (size_t)ib * blk) * rf), I * rf, gwb, bi * rf, bo, bi * rf, st);
+                    rc = fc::copy_block(gw_eff + 2 * (((size_t)ob * blk * I + (size_t)ib * blk) * rf), I * rf, w.gwb, bi * rf, bo, bi * rf, st);
             }
             if (rc != FC_OK) return rc;
         }
         if (p.nob > 1) {            // the sum over the output blocks, in block order
-            const int rc = fc::sum_parts(parts, gxb, (size_t)N * bi, pstride / 2, p.nob, st);
+            const int rc = fc::sum_parts(w.parts, w.gxb, (size_t)N * bi, w.pstride / 2, p.nob, st);
             if (rc != FC_OK) return rc;
         }
-        const int rc = fc::copy_block(gx + 2 * (size_t)ib * blk, I, gxb, bi, N, bi, st);
+        const int rc = fc::copy_block(gx + 2 * (size_t)ib * blk, I, w.gxb, bi, N, bi, st);
         if (rc != FC_OK) return rc;
     }
     if (params && params->bias_partials) {

@@ -72,9 +72,15 @@ def guarded(monkeypatch):
     import fieldconv_amd.blocks as blocks
     import fieldconv_amd.functional as Fn
     import fieldconv_amd.graph as graph
+    import fieldconv_amd.head as head
+    import fieldconv_amd.losses as losses
+    import fieldconv_amd.matching as matching
+    import fieldconv_amd.norm as norm
+    import fieldconv_amd.pooling as pooling
     import fieldconv_amd.transforms.fc_precomp as pre
+    import fieldconv_amd.transforms.support_graph as support
     g = GuardedTorch()
-    for mod in (Fn, blocks, graph, pre):
+    for mod in (Fn, blocks, graph, pre, norm, pooling, losses, head, matching, support):
         monkeypatch.setattr(mod, 'torch', g)
     # the host-side nodes in Python: the C++ nodes allocate inside torch's C++ API, where this stand-in does not reach
     monkeypatch.setenv('FIELDCONV_CPP_NODES', '0')
@@ -167,6 +173,113 @@ def test_no_write_outside_any_buffer_blocks(guarded, N, k, C, B, R):
     z = lift(pos, edges, sten[..., B:B + 2])
     torch.autograd.grad(z, [pos] + list(lift.parameters()), grad_outputs=_cplx(tuple(z.shape), gen, dev), allow_unused=True)
     n += guarded.check('LiftBlock')
+    assert n > 10
+
+
+def _close(what, got, want, tol=1e-4):
+    """float32 results against the families' float64 restatements.  The sums here have at most 131 terms, so rounding stays below
+    131 x 2^-24 = 8e-6 of the largest entry; 1e-4 leaves room for exp / log / sqrt.  A piece that overlaps another is wrong by O(1)."""
+    got = got.detach().cpu().numpy() if torch.is_tensor(got) else np.asarray(got)
+    want = np.asarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    scale = max(float(np.max(np.abs(want))), 1e-30)
+    err = float(np.max(np.abs(got - want))) / scale
+    assert err < tol, (what, err)
+
+
+def test_no_write_outside_and_no_overlap_inside_family_workspaces(guarded):
+    """TangentNorm, mesh pooling, the pair losses, the fused classification head, descriptor matching and the radius search, forward
+    and backward, at the smallest shapes that use every piece of their workspaces (an empty mesh, weights and gain; parts = 2, so that
+    the two-piece branches run; k = 3 for the two-array top-k; an epsilon that overfills rows).  Writes past a buffer trip the guard
+    bands; pieces that overlap INSIDE a workspace show as wrong values against the references the families' own tests use."""
+    import _head_ref as href
+    import _losses_ref as lref
+    import _matching_ref as mref
+    import _norm_ref as nref
+    from test_gpu_mesh_batch import pool_ref
+    from test_gpu_support_graph import radius_ref
+    from fieldconv_amd.head import linear_cross_entropy, linear_topk
+    from fieldconv_amd.losses import label_smoothing_loss, twin_loss
+    from fieldconv_amd.matching import match_descriptors
+    from fieldconv_amd.norm import tangent_norm
+    from fieldconv_amd.pooling import mesh_pool
+    from fieldconv_amd.transforms.support_graph import radius_edges
+    dev = torch.device('cuda:0')
+    rng = np.random.default_rng(11)
+
+    def D(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    # TangentNorm and pooling: (131, 5) complex64, an empty mesh first
+    ptr = [0, 0, 70, 131]
+    x, gy = nref.features(131, 5, 1).astype(np.complex64), nref.features(131, 5, 2).astype(np.complex64)
+    w, gain = nref.weights(131, 3).astype(np.float32), nref.gains(5, 4).astype(np.float32)
+    xd, gd = D(x).requires_grad_(True), D(gain).requires_grad_(True)
+    y = tangent_norm(xd, gd, D(np.asarray(ptr, dtype=np.int64)), D(w), 1e-5)
+    gx, gg = torch.autograd.grad(y, [xd, gd], grad_outputs=D(gy))
+    want = (nref.forward(x, ptr, w, gain, 1e-5, np.float64),) + tuple(nref.backward(x, gy, ptr, w, gain, 1e-5, np.float64))
+    for name, got, ref in zip(('y', 'gx', 'ggain'), (y, gx, gg), want):
+        _close('tangent_norm ' + name, got, np.asarray(ref).reshape(tuple(got.shape)))
+    n = guarded.check('tangent_norm')
+    g = rng.standard_normal((3, 5)).astype(np.float32)
+    for soft_abs, xin in ((True, x), (False, np.ascontiguousarray(x.real))):
+        xp = D(xin).requires_grad_(True)
+        out = mesh_pool(xp, D(np.asarray(ptr, dtype=np.int64)), 'mean', soft_abs)
+        gxp, = torch.autograd.grad(out, [xp], grad_outputs=D(g))
+        o_ref, g_ref = pool_ref(xin, ptr, 'mean', soft_abs, g.astype(np.float64))
+        _close('mesh_pool out', out, o_ref)
+        _close('mesh_pool gx', gxp, g_ref)
+    n += guarded.check('mesh_pool')
+
+    # the pair losses
+    xS, xT = rng.standard_normal((37, 6)).astype(np.float32), rng.standard_normal((41, 6)).astype(np.float32)
+    pp = np.stack((rng.integers(0, 41, 9), rng.integers(0, 37, 9)), 1).astype(np.int64)
+    nn = np.stack((rng.integers(0, 41, 11), rng.integers(0, 37, 11)), 1).astype(np.int64)
+    yN = rng.random(11).astype(np.float32)
+    a, b = D(xS).requires_grad_(True), D(xT).requires_grad_(True)
+    loss = twin_loss(a, b, D(pp), D(nn), D(yN), 5.0)
+    gS, gT = torch.autograd.grad(loss.sum(), [a, b])
+    lp, ln, gS_ref, gT_ref = lref.twin_loss(xS, xT, pp, nn, yN, 5.0)
+    _close('twin_loss', loss.reshape(()), lp + ln)
+    _close('twin_loss gS', gS, gS_ref)
+    _close('twin_loss gT', gT, gT_ref)
+    pred, tgt = rng.standard_normal((33, 7)).astype(np.float32), rng.integers(0, 7, 33).astype(np.int64)
+    pd_ = D(pred).requires_grad_(True)
+    loss = label_smoothing_loss(pd_, D(tgt), 7, 0.1)
+    gp, = torch.autograd.grad(loss.sum(), [pd_])
+    l_ref, g_ref = lref.label_smoothing(pred, tgt, 7, 0.1)
+    _close('label_smoothing', loss.reshape(()), l_ref)
+    _close('label_smoothing grad', gp, g_ref)
+    n += guarded.check('losses')
+
+    # the fused head with two parts: forward, weight gradient and top-k all take their two-piece layouts
+    h, W, bias = (rng.standard_normal(s).astype(np.float32) for s in ((70, 8), (5, 8), (5,)))
+    target = rng.integers(0, 5, 70).astype(np.int64)
+    hd, Wd, bd = (D(t).requires_grad_(True) for t in (h, W, bias))
+    loss = linear_cross_entropy(hd, Wd, bd, D(target), 'mean', 0.1, -100, 2)
+    grads = torch.autograd.grad(loss, [hd, Wd, bd])
+    want = href.head(h, W, bias, target, 'mean', 0.1, -100)
+    for name, got, ref in zip(('loss', 'g_h', 'g_W', 'g_b'), (loss.reshape(()),) + tuple(grads), want):
+        _close('linear_cross_entropy ' + name, got, ref)
+    idx, zk = linear_topk(D(h), D(W), D(bias), 3, 2)
+    z = href.logits(h, W, bias)
+    _close('linear_topk values', zk, -np.sort(-z, axis=1)[:, :3])
+    _close('linear_topk classes', zk, np.take_along_axis(z, idx.cpu().numpy(), 1))
+    n += guarded.check('head')
+
+    # matching with two parts (features as the family's tests draw them), and the radius search with overfull rows
+    mS, mT = (0.9 * rng.random((37, 6))).astype(np.float32), (0.9 * rng.random((41, 6))).astype(np.float32)
+    idx, d2 = match_descriptors(D(mS), D(mT), k=2, parts=2)
+    i_ref, d_ref = mref.topk(mS, mT, 2)
+    assert np.array_equal(idx.cpu().numpy(), i_ref)
+    _close('match d2', d2, d_ref)
+    n += guarded.check('matching')
+    pos = rng.random((200, 3)).astype(np.float32)
+    edges = radius_edges(D(pos), 0.35, 8).cpu().numpy()
+    ref = radius_ref(pos, 0.35, 8)
+    assert np.bincount(radius_ref(pos, 0.35, 512)[:, 0], minlength=200).max() > 8         # some rows are overfull
+    assert edges.shape == ref.shape and np.array_equal(edges, ref)
+    n += guarded.check('radius')
     assert n > 10
 
 
