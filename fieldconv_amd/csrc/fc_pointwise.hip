@@ -2,6 +2,9 @@
 //   TangentLin    (reference nn/tangent_lin.py:27-29)   dense complex channel mix on MFMA
 //   TangentNonLin (reference nn/tangent_nonlin.py:24-35) modReLU with the origin-box rule
 // plus their adjoints (the reference leaves those to torch autograd).
+#include <stdio.h>
+#include <string.h>
+
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
 
@@ -28,6 +31,11 @@ constexpr int kLinTiles = 4;      // output tiles accumulated together
 constexpr int kLinStage = 16;     // filter entries in flight per thread while staging
 
 __host__ __device__ inline int lin_plane_floats(int M, int K) { return round_up(M, 16) * slab_stride(round_up(2 * K, 16)); }
+// what the staged kernel derives from its arguments, in one place each for the kernel and for the host's account of a launch (lin_route):
+// k blocks of 16 real entries, 16-vertex blocks between two trips of a wavefront, and whether a row is loaded as float4s
+__host__ __device__ inline int lin_k_blocks(int K) { return round_up(2 * K, 16) / 16; }
+__host__ __device__ inline int lin_block_step(int grid, int split) { return split ? grid : grid * kLinWaves; }
+__host__ __device__ inline bool lin_vector_loads(int K, bool rows_aligned) { return (K & 1) == 0 && rows_aligned; }
 
 __device__ __forceinline__ void lin_load_fragments(float4 (&a)[kLinChunk], const float* row, int kc, int fq, int K, bool vec,
                                                    float keep) {
@@ -70,14 +78,14 @@ __global__ __launch_bounds__(kLinThreads) void tangent_lin_kernel(const float2* 
     float* Wi = lds + MP * KS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int fr = lane & 15, fq = lane >> 4;
-    const int nblocks = (N + 15) / 16, MT = MP / 16, KB = KR / 16;
+    const int nblocks = (N + 15) / 16, MT = MP / 16, KB = lin_k_blocks(K);
     const float* in_f = reinterpret_cast<const float*>(in);
-    const bool vec = (K & 1) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;       // 16-byte aligned rows
+    const bool vec = lin_vector_loads(K, (reinterpret_cast<uintptr_t>(in) & 15) == 0);       // 16-byte aligned rows
 
     // split (meshes whose 16-vertex blocks cannot occupy the chip with four of them per workgroup): a workgroup takes ONE block at a time
     // and its four wavefronts share the block's output tiles -- a wavefront's serial chain of fp32 MFMAs (32 cycles each) is a quarter as
     // long, the input rows are read by all four (L1 hits).  Same sums in the same order: bit-identical to the unsplit walk.
-    const int bstep = split ? gridDim.x : gridDim.x * kLinWaves;
+    const int bstep = lin_block_step(gridDim.x, split);
     const int tcount = split ? 1 : kLinTiles, mstart = split ? wave : 0, mstride = split ? kLinWaves : kLinTiles;
     // first input fragments of this wavefront: in flight while the filter is staged
     const int blk0 = split ? blockIdx.x : blockIdx.x * kLinWaves + wave;
@@ -442,16 +450,45 @@ static int lin_grid(int N) {
 // one 16-vertex block per workgroup at a time, its output tiles dealt to the four wavefronts (tangent_lin_kernel: split), when there is
 // more than one tile and the blocks alone cannot give every SIMD of the chip work
 static bool lin_split(int N, int M) { return M > 16 && (N + 15) / 16 <= 8 * num_cus(); }
-// the walk without LDS (tangent_lin_direct_kernel): K input channels, rows and filter 16-byte / 8-byte aligned
-static bool lin_direct(const void* in, const float* wre, const float* wim, int K, int ldw, bool transposed) {
+// the walk without LDS (tangent_lin_direct_kernel): K input channels; aligned: the input rows 16-byte aligned and, in the forward launch, the
+// filter rows 8-byte aligned (lin_aligned)
+static bool lin_direct(bool aligned, int K) {
     static const bool off = [] { const char* e = dev_env("FC_LIN_DIRECT"); return e && atoi(e) == 0; }();       // development: the staged walk
     if (off) return false;
-    if (K % 8 != 0 || K > 8 * kLinDirectKB || (reinterpret_cast<uintptr_t>(in) & 15)) return false;
+    return aligned && K % 8 == 0 && K <= 8 * kLinDirectKB;
+}
+static bool lin_aligned(const void* in, const float* wre, const float* wim, int ldw, bool transposed) {
+    if (reinterpret_cast<uintptr_t>(in) & 15) return false;
     return transposed || ((ldw & 1) == 0 && (reinterpret_cast<uintptr_t>(wre) & 7) == 0 && (reinterpret_cast<uintptr_t>(wim) & 7) == 0);
 }
 static int lin_grid_split(int N) {
     const int nblocks = (N + 15) / 16;
     return nblocks < 4 * num_cus() ? nblocks : 4 * num_cus();
+}
+// Which kernel a launch of the (N, K, M) product takes, and its grid: the launchers and fc_tangent_lin_describe both ask here.
+struct LinRoute { bool direct, split; int grid; size_t lds; };
+static LinRoute lin_route(int N, int K, int M, bool aligned) {
+    LinRoute r;
+    r.direct = M > 16 && lin_direct(aligned, K);
+    r.split = lin_split(N, M);
+    r.grid = r.direct || r.split ? lin_grid_split(N) : lin_grid(N);
+    r.lds = 2 * (size_t)lin_plane_floats(M, K) * sizeof(float);       // (the staged kernel's; the launchers refuse a shape beyond kMaxLds)
+    return r;
+}
+template <bool TRANSPOSED>
+static int lin_launch(const float2* in, const float* wre, const float* wim, float2* out, const float2* addend, int N, int K, int M, int ldw,
+                      hipStream_t s) {
+    const LinRoute r = lin_route(N, K, M, lin_aligned(in, wre, wim, ldw, TRANSPOSED));
+    if (r.lds > kMaxLds) return FC_ERR_UNSUPPORTED;
+    if (r.direct) {
+        hipLaunchKernelGGL(tangent_lin_direct_kernel<TRANSPOSED>, dim3(r.grid), dim3(kLinThreads), 0, s, in, wre, wim, out, addend, N, K, M, ldw);
+        return FC_OK;
+    }
+    static bool lds_ok[kMaxDevices] = {};
+    if (!allow_full_lds(reinterpret_cast<const void*>(tangent_lin_kernel<TRANSPOSED>), r.lds, lds_ok)) return FC_ERR_LAUNCH;
+    hipLaunchKernelGGL(tangent_lin_kernel<TRANSPOSED>, dim3(r.grid), dim3(kLinThreads), r.lds, s, in, wre, wim, out, addend, N, K, M, ldw,
+                       r.split ? 1 : 0);
+    return FC_OK;
 }
 static int lin_gw_groups(int N) {
     const int nblocks = (N + 15) / 16;
@@ -462,16 +499,9 @@ int tangent_lin_backward_impl(const float* x, const float* gy, const float* re_w
                               float* g_re, float* g_im, void* workspace, size_t workspace_bytes, int N, int I, int O, hipStream_t s) {
     if (!x || !gy || !re_w || !im_w || !gx || !g_re || !g_im || N <= 0 || I <= 0 || O <= 0) return FC_ERR_BAD_ARGUMENT;
     if (!workspace || workspace_bytes < fc_tangent_lin_backward_workspace_bytes(N, I, O)) return FC_ERR_WORKSPACE;
-    const size_t lds = 2 * (size_t)lin_plane_floats(I, O) * sizeof(float);
-    if (lds > kMaxLds) return FC_ERR_UNSUPPORTED;
-    const bool split = lin_split(N, I);
-    if (I > 16 && lin_direct(gy, re_w, im_w, O, I, true))
-        hipLaunchKernelGGL(tangent_lin_direct_kernel<true>, dim3(lin_grid_split(N)), dim3(kLinThreads), 0, s, reinterpret_cast<const float2*>(gy),
-                           re_w, im_w, reinterpret_cast<float2*>(gx), reinterpret_cast<const float2*>(gx_addend), N, O, I, I);
-    else
-        hipLaunchKernelGGL(tangent_lin_kernel<true>, dim3(split ? lin_grid_split(N) : lin_grid(N)), dim3(kLinThreads), lds, s,
-                           reinterpret_cast<const float2*>(gy), re_w, im_w, reinterpret_cast<float2*>(gx),
-                           reinterpret_cast<const float2*>(gx_addend), N, O, I, I, split ? 1 : 0);
+    const int rc = lin_launch<true>(reinterpret_cast<const float2*>(gy), re_w, im_w, reinterpret_cast<float2*>(gx),
+                                    reinterpret_cast<const float2*>(gx_addend), N, O, I, I, s);
+    if (rc != FC_OK) return rc;
     float2* part = reinterpret_cast<float2*>(workspace);
     const int ng = lin_gw_groups(N);
     const int pairs = ((O + 15) / 16) * ((I + 15) / 16);
@@ -489,18 +519,30 @@ extern "C" {
 int fc_tangent_lin_forward(const float* x, const float* re_w, const float* im_w, float* y, int32_t N, int32_t I,
                            int32_t O, void* stream) {
     if (!x || !re_w || !im_w || !y || N <= 0 || I <= 0 || O <= 0) return FC_ERR_BAD_ARGUMENT;
-    const size_t lds = 2 * (size_t)fc::lin_plane_floats(O, I) * sizeof(float);
-    if (lds > fc::kMaxLds) return FC_ERR_UNSUPPORTED;
-    const bool split = fc::lin_split(N, O);
-    if (O > 16 && fc::lin_direct(x, re_w, im_w, I, I, false))
-        hipLaunchKernelGGL(fc::tangent_lin_direct_kernel<false>, dim3(fc::lin_grid_split(N)), dim3(fc::kLinThreads), 0,
-                           static_cast<hipStream_t>(stream), reinterpret_cast<const float2*>(x), re_w, im_w, reinterpret_cast<float2*>(y),
-                           (const float2*)nullptr, N, I, O, I);
-    else
-        hipLaunchKernelGGL(fc::tangent_lin_kernel<false>, dim3(split ? fc::lin_grid_split(N) : fc::lin_grid(N)), dim3(fc::kLinThreads), lds,
-                           static_cast<hipStream_t>(stream), reinterpret_cast<const float2*>(x), re_w, im_w,
-                           reinterpret_cast<float2*>(y), (const float2*)nullptr, N, I, O, I, split ? 1 : 0);
+    const int rc = fc::lin_launch<false>(reinterpret_cast<const float2*>(x), re_w, im_w, reinterpret_cast<float2*>(y), nullptr, N, I, O, I,
+                                         static_cast<hipStream_t>(stream));
+    if (rc != FC_OK) return rc;
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+}
+
+int fc_tangent_lin_describe(int32_t N, int32_t K, int32_t M, int32_t transposed, int32_t aligned, char* buffer, size_t buffer_bytes) {
+    if (!buffer || buffer_bytes < 2 || N <= 0 || K <= 0 || M <= 0 || (transposed != 0 && transposed != 1) || (aligned != 0 && aligned != 1))
+        return FC_ERR_BAD_ARGUMENT;
+    const fc::LinRoute r = fc::lin_route(N, K, M, aligned != 0);
+    if (r.lds > fc::kMaxLds) return FC_ERR_BAD_ARGUMENT;        // (the launchers refuse the shape)
+    const int blocks = (N + 15) / 16;
+    const int step = r.direct ? r.grid : fc::lin_block_step(r.grid, r.split ? 1 : 0);       // (the direct kernel: one block per workgroup)
+    const int trips = (blocks + step - 1) / step;
+    char line[256];
+    if (r.direct)
+        snprintf(line, sizeof(line), "direct grid=%d blocks=%d trips=%d cus=%d", r.grid, blocks, trips, fc::num_cus());
+    else
+        snprintf(line, sizeof(line), "staged split=%d loads=%s tiles=%d kchunks=%d lds=%zu grid=%d blocks=%d trips=%d cus=%d", r.split ? 1 : 0,
+                 fc::lin_vector_loads(K, aligned != 0) ? "vector" : "scalar", fc::round_up(M, 16) / 16,
+                 (fc::lin_k_blocks(K) + fc::kLinChunk - 1) / fc::kLinChunk, r.lds, r.grid, blocks, trips, fc::num_cus());
+    if (strlen(line) + 1 > buffer_bytes) return -2;
+    memcpy(buffer, line, strlen(line) + 1);
+    return FC_OK;
 }
 
 size_t fc_tangent_lin_backward_workspace_bytes(int32_t N, int32_t I, int32_t O) {

@@ -297,6 +297,16 @@ size_t fc_tangent_lin_backward_workspace_bytes(int32_t N, int32_t I, int32_t O);
 int fc_tangent_lin_backward(const float* x, const float* gy, const float* re_w, const float* im_w,
                             float* gx, float* g_re, float* g_im, void* workspace, size_t workspace_bytes,
                             int32_t N, int32_t I, int32_t O, void* stream);
+/* Which kernel one launch of the (N, K, M) product takes in this process, as one line of text (fc_describe_kernels' idiom; no GPU
+ * work, and without a device the CU count counts as 256).  The forward pass is the launch K = I, M = O, transposed = 0; the input
+ * gradient K = O, M = I, transposed = 1.  aligned: 1 when the input rows (x, or gy when transposed) start on a 16-byte boundary and,
+ * in the forward launch, re_w and im_w on 8-byte ones with an even row length; with 0 the staged kernel loads its rows element by
+ * element.  The line reads
+ *     direct grid=G blocks=B trips=T cus=C
+ *     staged split=0|1 loads=vector|scalar tiles=MT kchunks=KC lds=BYTES grid=G blocks=B trips=T cus=C
+ * (blocks: 16-vertex blocks; trips: the most blocks one wavefront walks; tiles: 16-channel output tiles; kchunks: sets of input
+ * fragments a wavefront loads per block).  FC_ERR_BAD_ARGUMENT for sizes the launchers refuse, -2 when the buffer is too small. */
+int fc_tangent_lin_describe(int32_t N, int32_t K, int32_t M, int32_t transposed, int32_t aligned, char* buffer, size_t buffer_bytes);
 
 /* ---- TangentNonLin.forward (modReLU), reference nn/tangent_nonlin.py:24-35 --------------- *
  * y = relu(|x| + b_c) x/|x| outside the origin box, x inside it.  bias: C floats. */

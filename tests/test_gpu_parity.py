@@ -1121,7 +1121,10 @@ def test_conv_epilogue_fusion_matches_separate_operators(dev, monkeypatch, N, k)
 
 
 @pytest.mark.parametrize('N,k,cin,cout,frontload,B', [(700, 14, 16, 24, False, 2), (9000, 8, 24, 16, True, 2), (200, 96, 48, 48, False, 2),
-                                                      (1024, 128, 48, 48, False, 2), (500, 20, 64, 64, False, 3), (300, 12, 8, 8, True, 1)])
+                                                      (1024, 128, 48, 48, False, 2), (500, 20, 64, 64, False, 3), (300, 12, 8, 8, True, 1),
+                                                      # (24 -> 20 channels: the residual branch's input gradient is TangentLin's transposed launch with
+                                                      #  K = 20, M = 24 -- the staged split kernel -- and addend == out)
+                                                      (300, 10, 24, 20, False, 2)])
 def test_block_level_entry_points_match_the_per_operator_path(dev, monkeypatch, N, k, cin, cout, frontload, B):
     """FCResNetBlock / ECHOBlock / LiftBlock through ONE native call per pass (csrc/fc_blocks.hip: fc_resnet_block_*, fc_echo_block_*,
     fc_lift_block_*; reference nn/fc_resnet_block.py:84-88, nn/echo_block.py:93-103, nn/lift_block.py:53-55) against the same modules
