@@ -235,6 +235,7 @@ SIGNATURES = {
     'fc_tangent_norm_workspace_bytes': (_sz, [_c_int32] * 4),
     'fc_tangent_norm_forward': (ctypes.c_int, [_vp] * 4 + [_c_int32] * 4 + [ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
     'fc_tangent_norm_backward': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 4 + [_vp, _vp, _vp, _sz, _vp]),
+    'fc_knn_weights': (ctypes.c_int, [_vp] * 3 + [_c_int32] * 4 + [_vp] * 3),
 }
 
 _LIB = None

@@ -1213,4 +1213,5 @@ from .geodesic_sampling import (geodesic_farthest_point_sample, geodesic_farthes
                                 geodesic_radius_edges)
 from .logmap import log_map_transport, vertex_frames          # noqa: E402,F401  (csrc/fc_logmap.hip)
 from .transfer import TransferPlan, level_transfer, sample_cells, tangent_transfer          # noqa: E402,F401  (csrc/fc_transfer.hip)
+from .transfer import interpolation_plan, knn_weights, vertex_interpolation          # noqa: E402,F401  (csrc/fc_interp.hip)
 from .norm import tangent_norm          # noqa: E402,F401  (csrc/fc_norm.hip)

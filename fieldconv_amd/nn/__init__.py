@@ -15,7 +15,8 @@ from .linear_cross_entropy import LinearCrossEntropy
 from ..head import vertex_accuracy
 from .tangent_pool import TangentPool, TangentUnpool
 from .tangent_norm import TangentNorm
+from .tangent_interpolate import TangentInterpolate
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
            'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval',
-           'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'TangentNorm', 'MeshPool']
+           'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'TangentNorm', 'TangentInterpolate', 'MeshPool']

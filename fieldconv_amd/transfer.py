@@ -4,7 +4,8 @@
 
 with a deterministic gradient, the plan that holds its two CSRs, and the glue that builds the plans of a level pair from the
 package's own geodesics: nearest-sample cells (geodesic.nearest_sample), sample masses (data.w) and the transport phase along a
-shortest-path tree (logmap.log_map_transport).
+shortest-path tree (logmap.log_map_transport).  interpolation_plan / vertex_interpolation build the smooth counterpart of the
+unpool plan: every receiver from its k nearest coarse samples with inverse-distance weights (csrc/fc_interp.hip).
 
 A tangent-vector feature lives in its sample's frame, so a plain mean over a cell is wrong: every term is parallel-transported
 into the receiving sample's frame first, which is a multiplication by a unit complex number -- the phase of a row.  Real
@@ -288,3 +289,152 @@ def level_transfer(pos, face, sample_idx, coarse, w_fine, graph=None, diagonals=
         unpool = TransferPlan(torch.stack((member, c), 1), torch.ones_like(weight), xp, n_out=S_f, n_in=S_c)
         pool = TransferPlan(torch.stack((c, member), 1), weight, xp, n_out=S_c, n_in=S_f, conj_phase=True)
     return (pool, unpool, cell.to(pos.device), n_outside) if return_cells else (pool, unpool)
+
+
+# ------------------------------------------------------------------ interpolation from the k nearest coarse samples
+KNN_MAX = 16          # fc_knn_weights keeps a row's best k in registers: 1 <= k <= 16
+
+
+def _check_knn(k, power, what):
+    try:
+        ok = not isinstance(k, bool) and int(k) == k and 1 <= k <= KNN_MAX
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'{what}: k must be an integer in [1, {KNN_MAX}], got {k!r}')
+    if isinstance(power, bool) or power not in (1, 2):
+        raise ValueError(f'{what}: power must be 1 or 2, got {power!r}')
+    return int(k), int(power)
+
+
+def knn_weights(rowptr, cand, dist, k=3, power=2):
+    """(sel (n_f,k) int32, weight (n_f,k) float32) of csrc/fc_interp.hip (fc_knn_weights) for a CSR of candidates by receiving
+    row: rowptr (n_f+1,) int32, cand (n_slots,) int32 coarse positions, dist (n_slots,) float32 >= 0 and finite, on a ROCm device.
+    With m = min(k, row length), sel[f, :m] are the slots of the row's m smallest candidates by (dist, cand, slot), in that
+    order, and weight[f, :m] their weights: 1, 0, ..., 0 when the nearest distance is 0, else u_i / s with q_i = d_i (power 1) or
+    d_i * d_i (power 2), u_i = 1 / max(q_i, 1e-30) and s = ((u_0 + u_1) + u_2) + ..., every operation rounded to float32 on its
+    own.  From rank m on sel is -1 and weight 0; an empty row has m = 0.  One launch, no atomics: two runs give the same bits."""
+    what = 'knn_weights'
+    k, power = _check_knn(k, power, what)
+    for t, name, dt in ((rowptr, 'rowptr', torch.int32), (cand, 'cand', torch.int32), (dist, 'dist', torch.float32)):
+        if not torch.is_tensor(t) or t.dim() != 1 or t.dtype != dt:
+            raise ValueError(f'{what}: {name} must be a 1-D {dt} tensor, got {(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}')
+    if rowptr.numel() < 1 or cand.shape != dist.shape:
+        raise ValueError(f'{what}: rowptr must hold n_f + 1 entries and cand and dist one entry per slot, got {tuple(rowptr.shape)}, '
+                         f'{tuple(cand.shape)} and {tuple(dist.shape)}')
+    if not rowptr.is_cuda or cand.device != rowptr.device or dist.device != rowptr.device:
+        raise RuntimeError(f'{what}: rowptr, cand and dist must be on one ROCm device; there is no CPU path')
+    n_f, n_slots = int(rowptr.numel()) - 1, int(cand.numel())
+    if n_f * k >= 2 ** 31:
+        raise ValueError(f'{what}: n_f * k must stay below 2^31, got {n_f} x {k}')
+    lib = _lib.load()
+    rowptr, cand, dist = rowptr.contiguous(), cand.contiguous(), dist.contiguous()
+    with torch.cuda.device(rowptr.device):
+        sel = torch.empty((n_f, k), dtype=torch.int32, device=rowptr.device)
+        weight = torch.empty((n_f, k), dtype=torch.float32, device=rowptr.device)
+        _lib.check(lib.fc_knn_weights(_ptr(rowptr), _ptr(cand) if n_slots else None, _ptr(dist) if n_slots else None, n_f, n_slots, k, power,
+                                      _ptr(sel), _ptr(weight), _stream()), 'fc_knn_weights')
+    return sel, weight
+
+
+def interpolation_plan(pos, face, sample_idx, coarse, k=3, power=2, radius=None, graph=None, diagonals=False, pos_ptr=None, ptr=None,
+                       coarse_ptr=None, return_rows=False, *, _what='interpolation_plan'):
+    """The TransferPlan (S_f x S_c) that carries features of the coarse samples sample_idx[coarse] (S_c,) to the fine samples
+    sample_idx (S_f,) ascending as PointNet++'s feature propagation does: every fine sample receives the inverse-distance-weighted
+    combination of its k nearest coarse samples, each term parallel-transported into the receiver's frame first.  Where
+    level_transfer's unpool is piecewise constant over the cells, this is continuous across their boundaries.
+
+    radius  None: fl32(2 far) moved one float32 step upward, far the largest finite sample_cells distance, so that a fine sample
+            in a cell has at least its own coarse sample as a candidate.  When far == 0 every member is a coarse sample (or lies
+            on one) and the plan is [f, cell[f]] with weight 1 and phase 1.  Given: a finite number > 0.
+    candidates   every pair (c, f) with d_a[sample_idx[f]] < fl32(radius), strict, d_a the single-source field of vertex
+            a = sample_idx[coarse[c]] bounded by radius: geodesic_radius_edges' relation, coarse queries only, never truncated.
+            (All S_f balls are solved and the coarse ones kept: a restriction of the ball search to some queries does not exist.)
+    rows    [coarse[c], f] go through log_map_transport(..., bound=radius): dist is its logMag, the distance the convolution
+            sees, xp its phase.  Every row is reached by construction; that is checked.
+    plan    per fine sample f its candidates ascending in c go to knn_weights(k, power); its m = min(k, candidates) rows [f, c_i]
+            follow in rank order with weight w_i and phase xp_i (unpool's convention, conj_phase False).  The zero-weight rows of
+            an exact hit are kept.  A fine sample without a candidate (cell -1, or further than radius from every coarse sample)
+            has no row: zero output.
+    graph, diagonals, pos_ptr / ptr / coarse_ptr: as in level_transfer; in a batch no candidate crosses meshes.
+    return_rows: also (rowptr (S_f+1,) int32, cand (E,) int32, dist (E,) float32, xp (E,) complex64), the candidate CSR the
+    selection ran on.  Nothing here is differentiable; the operator's gradient runs on plan.adjoint()."""
+    what = _what
+    _check_mesh(pos, face, what)
+    _check_diagonals(graph, diagonals, what)
+    V = int(pos.shape[0])
+    _check_index(sample_idx, V, what, 'sample_idx')
+    S_f = int(sample_idx.numel())
+    if S_f > 1 and not bool((sample_idx[1:] > sample_idx[:-1]).all()):
+        raise ValueError(f'{what}: sample_idx must be strictly ascending')
+    host_c = _check_coarse(coarse, S_f, what)
+    S_c = len(host_c)
+    _check_batch(pos_ptr, ptr, coarse_ptr, V, S_f, host_c, what)
+    k, power = _check_knn(k, power, what)
+    if radius is not None:
+        radius = _check_bound(radius, what)
+    if not isinstance(return_rows, bool):
+        raise ValueError(f'{what}: return_rows must be True or False, got {return_rows!r}')
+    from .geodesic_sampling import geodesic_radius_edges
+    dev = _device_of(pos)
+    if graph is None:
+        graph = mesh_edge_graph(pos, face, diagonals)
+    trivial = False
+    if radius is None:
+        cell, dist = sample_cells(pos, face, sample_idx, coarse, graph=graph, pos_ptr=pos_ptr, ptr=ptr, coarse_ptr=coarse_ptr)
+        cell, dist = cell.to(dev), dist.to(dev)
+        inside = (cell >= 0) & torch.isfinite(dist)
+        far = float(dist[inside].max()) if bool(inside.any()) else 0.0
+        if far > 0:
+            up = torch.nextafter(torch.tensor(2.0, dtype=torch.float32) * torch.tensor(far, dtype=torch.float32),
+                                 torch.tensor(float('inf'), dtype=torch.float32))
+            radius = _check_bound(float(up), what)
+        else:
+            trivial = True
+    with torch.cuda.device(dev):
+        if trivial:          # no tree to grow: every member sits on its coarse sample
+            f = torch.nonzero(inside)[:, 0]
+            c = cell[f]
+            mag = torch.zeros(int(f.numel()), dtype=torch.float32, device=dev)
+            xp = torch.ones(int(f.numel()), dtype=torch.complex64, device=dev)
+        else:
+            edges = geodesic_radius_edges(pos, face, sample_idx, radius, max_num_neighbors=S_f, pos_ptr=pos_ptr, sample_ptr=ptr,
+                                          graph=graph).to(dev)          # S_f neighbours at most: the cap cannot bite
+            where = torch.full((S_f,), -1, dtype=torch.int64, device=dev)
+            where[coarse.to(dev)] = torch.arange(S_c, device=dev)
+            c = where[edges[:, 0]]
+            keep = c >= 0
+            c, a, f = c[keep], edges[keep, 0], edges[keep, 1]
+            if int(f.numel()):
+                mag, _, xp, reached = log_map_transport(pos, face, sample_idx, torch.stack((a, f), 1), radius, graph=graph, pos_ptr=pos_ptr,
+                                                        ptr=ptr, return_reached=True)
+                if not bool(reached.all()):
+                    raise _lib.FieldConvNativeError(f'{what}: {int((~reached).sum())} candidate rows inside the radius were not reached by '
+                                                    'the transport tree: the ball search and the log map disagree')
+                mag, xp = mag.to(dev), xp.to(dev)
+            else:
+                mag = torch.zeros(0, dtype=torch.float32, device=dev)
+                xp = torch.ones(0, dtype=torch.complex64, device=dev)
+        order = torch.sort(f, stable=True)          # grouped by receiver; the rows came grouped by c ascending, so c ascends in a group
+        rowptr = torch.searchsorted(order.values.contiguous(), torch.arange(S_f + 1, device=dev)).to(torch.int32)
+        cand = c[order.indices].to(torch.int32).contiguous()
+        mag, xp = mag[order.indices].contiguous(), xp[order.indices].contiguous()
+        sel, w = knn_weights(rowptr, cand, mag, k, power)
+        taken = sel >= 0
+        slot = sel[taken].to(torch.int64)          # row-major: by receiver, then rank
+        recv = torch.nonzero(taken)[:, 0]
+        plan = TransferPlan(torch.stack((recv, cand[slot].to(torch.int64)), 1), w[taken], xp[slot], n_out=S_f, n_in=S_c)
+    return (plan, rowptr, cand, mag, xp) if return_rows else plan
+
+
+def vertex_interpolation(pos, face, sample_idx, k=3, power=2, radius=None, graph=None, diagonals=False, pos_ptr=None, ptr=None):
+    """The TransferPlan (V x S) of interpolation_plan with every vertex of pos as the fine level and the samples sample_idx (S,)
+    strictly ascending as the coarse one: it carries sample-level logits (real features take the weights alone) or tangent
+    features, transported into vertex_frames, to the full mesh.  The row of a sampled vertex is the identity.  pos_ptr, ptr: both
+    None, or the range tables of a MeshBatch over pos and sample_idx; no row crosses meshes."""
+    what = 'vertex_interpolation'
+    _check_mesh(pos, face, what)
+    if (pos_ptr is None) != (ptr is None):
+        raise ValueError(f'{what}: pos_ptr and ptr go together (the ranges of a MeshBatch): give both or neither')
+    every = torch.arange(int(pos.shape[0]), dtype=torch.int64, device=sample_idx.device if torch.is_tensor(sample_idx) else None)
+    return interpolation_plan(pos, face, every, sample_idx, k, power, radius, graph, diagonals, pos_ptr, pos_ptr, ptr, _what=what)

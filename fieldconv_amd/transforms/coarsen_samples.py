@@ -5,7 +5,7 @@ on the ROCm device."""
 import torch
 
 from ..data.synthetic import SupportData
-from ..transfer import _check_coarse, level_transfer
+from ..transfer import _check_coarse, _check_knn, interpolation_plan, level_transfer
 from .compute_log_xport import ComputeLogXPort
 from .geodesic_support_graph import GeodesicSupportGraph
 from .support_graph import _check_epsilon, _check_k, farthest_point_sample, farthest_point_sample_batched
@@ -21,6 +21,9 @@ class CoarsenSamples(object):
         logMag, logAng, xp, w       ComputeLogXPort(epsilon, diagonals=...)
         pool, unpool    the TransferPlans of level_transfer (fine -> coarse, coarse -> fine), cell weights from fine.w
         cell, n_outside every fine sample's cell (a position in coarse, -1: in no cell) and how many are in none
+        interp          only with interpolate_k: the TransferPlan of interpolation_plan(k=interpolate_k, power=interpolate_power),
+                        coarse -> fine from the k nearest coarse samples, which nn.TangentInterpolate takes; the mesh's edge graph
+                        is then built once and shared with level_transfer
 
     so the coarse level is indistinguishable from a level built directly and FCPrecomp consumes it unchanged; nn.TangentPool and
     nn.TangentUnpool take it as their `level`.  The fine data is not modified.
@@ -35,7 +38,8 @@ class CoarsenSamples(object):
     over batch.ptr, min(n_coarse, n_b) samples per mesh) and yields a coarse MeshBatch with its own ptr, batch and edge_ptr; no
     cell crosses meshes: mesh for mesh what the single call gives.  With an explicit coarse on a batch give coarse_ptr too."""
 
-    def __init__(self, n_coarse, epsilon, max_num_neighbors=512, diagonals=False, coarse=None, coarse_ptr=None):
+    def __init__(self, n_coarse, epsilon, max_num_neighbors=512, diagonals=False, coarse=None, coarse_ptr=None, interpolate_k=None,
+                 interpolate_power=2):
         what = 'CoarsenSamples'
         if coarse is None and (isinstance(n_coarse, bool) or n_coarse is None or int(n_coarse) != n_coarse or n_coarse < 1):
             raise ValueError(f'{what}: n_coarse must be an integer >= 1, got {n_coarse!r}')
@@ -46,6 +50,9 @@ class CoarsenSamples(object):
             raise ValueError(f'{what}: diagonals must be True or False, got {diagonals!r}')
         self.diagonals = diagonals
         self.coarse, self.coarse_ptr = coarse, coarse_ptr
+        self.interpolate_k = self.interpolate_power = None
+        if interpolate_k is not None:
+            self.interpolate_k, self.interpolate_power = _check_knn(interpolate_k, interpolate_power, what)
 
     def _select(self, data, batched):
         """-> (coarse positions on pos's device, per-mesh counts or None)"""
@@ -96,11 +103,19 @@ class CoarsenSamples(object):
         out.coarse = coarse
         out = GeodesicSupportGraph(self.epsilon, max_num_neighbors=self.max_num_neighbors, diagonals=self.diagonals)(out)
         out = ComputeLogXPort(self.epsilon, diagonals=self.diagonals)(out)
-        out.pool, out.unpool, out.cell, out.n_outside = level_transfer(
-            pos, data.face, fine_idx, coarse, data.w, diagonals=self.diagonals, pos_ptr=data.pos_ptr if batched else None,
-            ptr=data.ptr if batched else None, coarse_ptr=out.ptr if batched else None, return_cells=True)
+        ranges = dict(pos_ptr=data.pos_ptr if batched else None, ptr=data.ptr if batched else None, coarse_ptr=out.ptr if batched else None)
+        if self.interpolate_k is None:
+            out.pool, out.unpool, out.cell, out.n_outside = level_transfer(pos, data.face, fine_idx, coarse, data.w, diagonals=self.diagonals,
+                                                                           return_cells=True, **ranges)
+            return out
+        from ..geodesic import mesh_edge_graph
+        graph = mesh_edge_graph(pos, data.face, self.diagonals)          # (the graph decides: diagonals stays False below)
+        out.pool, out.unpool, out.cell, out.n_outside = level_transfer(pos, data.face, fine_idx, coarse, data.w, graph=graph, return_cells=True,
+                                                                       **ranges)
+        out.interp = interpolation_plan(pos, data.face, fine_idx, coarse, self.interpolate_k, self.interpolate_power, graph=graph, **ranges)
         return out
 
     def __repr__(self):
-        return '{}(n_coarse={}, epsilon={}, max_num_neighbors={}{})'.format(self.__class__.__name__, self.n_coarse, self.epsilon,
-                                                                            self.max_num_neighbors, ', diagonals=True' if self.diagonals else '')
+        return '{}(n_coarse={}, epsilon={}, max_num_neighbors={}{}{})'.format(
+            self.__class__.__name__, self.n_coarse, self.epsilon, self.max_num_neighbors, ', diagonals=True' if self.diagonals else '',
+            '' if self.interpolate_k is None else f', interpolate_k={self.interpolate_k}, interpolate_power={self.interpolate_power}')

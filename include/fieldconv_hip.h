@@ -919,6 +919,19 @@ int fc_tangent_norm_backward(const void* x, const void* w, const int64_t* ptr, c
                              int32_t B, int32_t C, int32_t dtype, void* gx, void* ggain, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* ---- interpolation weights: the k nearest candidates of every row and their inverse-distance weights (csrc/fc_interp.hip) ------ *
+ * rowptr (n_f+1) / cand (n_slots) int32 / dist (n_slots) float32, >= 0 and finite: a CSR of candidates by receiving row, cand the
+ * coarse position.  1 <= k <= 16, power 1 or 2, else FC_ERR_BAD_ARGUMENT.  With m = min(k, row length):
+ *   sel (n_f, k) int32      the slots of the row's m smallest candidates by the key (dist as a float32 compare, cand, slot), in
+ *                           that order; -1 from rank m on
+ *   weight (n_f, k) float32 dist of rank 0 == 0: 1, 0, ..., 0.  Else q_i = d_i (power 1) or d_i * d_i (power 2),
+ *                           u_i = 1 / max(q_i, 1e-30), s = ((u_0 + u_1) + u_2) + ... in rank order, w_i = u_i / s: every operation
+ *                           a float32 operation rounded on its own.  0 from rank m on.
+ * An empty row gives m = 0.  rowptr entries are clamped to [0, n_slots] and to the row's own start.  One lane per row, no atomics:
+ * the same bits on every run.  No workspace, no allocation or synchronisation inside. */
+int fc_knn_weights(const int32_t* rowptr, const int32_t* cand, const float* dist, int32_t n_f, int32_t n_slots, int32_t k, int32_t power,
+                   int32_t* sel, float* weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
