@@ -66,6 +66,25 @@ __device__ __forceinline__ float wave_max_nonneg(float v) {
     return __int_as_float(__builtin_amdgcn_readlane(x, 63));
 }
 
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// Sum over a workgroup of WAVES wavefronts, valid in thread 0: xor tree inside each wavefront, then the wavefronts in index order.
+template <int WAVES>
+__device__ __forceinline__ double block_sum(double v, double* slots) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < WAVES; ++w) s += slots[w];
+    return s;
+}
+
 // Row gather with a 32-bit byte offset: base (wave-uniform, SGPR pair) + vertex * row bytes + lane part fits the
 // scalar-base form of global_load.  The offset is ONE v_mad_u32_u24 instead of v_mul_lo_u32 + v_add (measured: no visible
 // change -- the walks are not bound by their vector instructions, tools/ubench/walk.hip).  The callers guarantee

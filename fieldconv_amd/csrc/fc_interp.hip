@@ -12,20 +12,19 @@
 // samples, thousands, so the rows alone fill the device; a wavefront per row would leave most of its 64 lanes without a
 // candidate and pay a cross-lane sort for a list this small.  The lanes of a wavefront own neighbouring rows, whose slots are
 // neighbours in cand / dist, so their loads share cache lines although one load instruction is not contiguous.  A lane keeps the
-// best K entries sorted in registers: the loops over the list are unrolled over the compile-time K (4, 8 or 16, the least that
-// holds k), every index is static and nothing goes to scratch; a new slot is inserted by carrying the displaced entry down the
-// list, K compare-and-swaps per slot.  Lanes of one wavefront run as long as the longest of their rows.
+// best K entries (4, 8 or 16, the least that holds k) sorted in registers as a NearestCand list of fc_select.hpp, three planes
+// (dist, cand, slot), and inserts with list_insert_carry.  Lanes of one wavefront run as long as the longest of their rows.
 //
 // Nothing outside the buffers is touched whatever rowptr holds: its entries are clamped to [0, n_slots] and to the row's own
 // start, as fc_transfer clamps them.  No atomics, no workspace, one launch: two runs give the same bits.
 #include "../../include/fieldconv_hip.h"
 #include "fc_common.hpp"
+#include "fc_select.hpp"
 
 namespace fc {
 
 constexpr int kKnnThreads = 256;
 constexpr int kKnnMax = 16;
-constexpr int kKnnNone = 0x7fffffff;          // the slot and cand of a list entry nothing was put into
 
 template <int K>
 __global__ __launch_bounds__(kKnnThreads) void knn_weights_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ cand,
@@ -38,33 +37,8 @@ __global__ __launch_bounds__(kKnnThreads) void knn_weights_kernel(const int32_t*
 
     float bd[K];
     int bc[K], bs[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        bd[j] = __builtin_inff();
-        bc[j] = kKnnNone;
-        bs[j] = kKnnNone;
-    }
-    for (int e = e0; e < e1; ++e) {
-        float d = dist[e];
-        int c = cand[e], s = e;
-        // slots arrive ascending, so an entry already listed has the lower slot: the new slot goes in front of the first entry it
-        // is strictly less than by (dist, cand), a tie in both leaving the earlier slot in front.  From there on the displaced
-        // entry is carried: the list is sorted, so it goes in front of every entry behind it, equal ones included.
-        bool carried = false;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const bool less = carried || d < bd[j] || (d == bd[j] && c < bc[j]);
-            carried = less;
-            const float td = bd[j];
-            const int tc = bc[j], ts = bs[j];
-            bd[j] = less ? d : td;
-            bc[j] = less ? c : tc;
-            bs[j] = less ? s : ts;
-            d = less ? td : d;
-            c = less ? tc : c;
-            s = less ? ts : s;
-        }
-    }
+    list_clear<NearestCand>(bd, bc, bs);
+    for (int e = e0; e < e1; ++e) list_insert_carry<NearestCand>(bd, bc, bs, dist[e], cand[e], e);
 
     const int m = min(k, e1 - e0);
     float u[K];
@@ -82,7 +56,7 @@ __global__ __launch_bounds__(kKnnThreads) void knn_weights_kernel(const int32_t*
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         if (j < k) {
-            const bool in = j < m && bs[j] != kKnnNone;
+            const bool in = j < m && bs[j] != kSelNone;
             const float w = exact ? (j == 0 ? 1.0f : 0.0f) : __fdiv_rn(u[j], sum);
             srow[j] = in ? bs[j] : -1;
             wrow[j] = in ? w : 0.0f;
@@ -92,19 +66,6 @@ __global__ __launch_bounds__(kKnnThreads) void knn_weights_kernel(const int32_t*
 
 }  // namespace fc
 
-namespace {
-
-template <int K>
-int knn_launch(const int32_t* rowptr, const int32_t* cand, const float* dist, int32_t n_f, int32_t n_slots, int32_t k, int32_t power,
-               int32_t* sel, float* weight, hipStream_t s) {
-    const unsigned blocks = (unsigned)(((long long)n_f + fc::kKnnThreads - 1) / fc::kKnnThreads);
-    hipLaunchKernelGGL((fc::knn_weights_kernel<K>), dim3(blocks), dim3(fc::kKnnThreads), 0, s, rowptr, cand, dist, (int)n_f, (int)n_slots,
-                       (int)k, (int)power, sel, weight);
-    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
-}
-
-}  // namespace
-
 extern "C" {
 
 int fc_knn_weights(const int32_t* rowptr, const int32_t* cand, const float* dist, int32_t n_f, int32_t n_slots, int32_t k, int32_t power,
@@ -113,9 +74,12 @@ int fc_knn_weights(const int32_t* rowptr, const int32_t* cand, const float* dist
     if (n_f == 0) return FC_OK;
     if (!rowptr || !sel || !weight || (n_slots > 0 && (!cand || !dist))) return FC_ERR_BAD_ARGUMENT;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (k <= 4) return knn_launch<4>(rowptr, cand, dist, n_f, n_slots, k, power, sel, weight, s);
-    if (k <= 8) return knn_launch<8>(rowptr, cand, dist, n_f, n_slots, k, power, sel, weight, s);
-    return knn_launch<16>(rowptr, cand, dist, n_f, n_slots, k, power, sel, weight, s);
+    const unsigned blocks = (unsigned)(((long long)n_f + fc::kKnnThreads - 1) / fc::kKnnThreads);
+    fc::dispatch_k<4, 8, 16>(k, [&](auto rung) {
+        hipLaunchKernelGGL((fc::knn_weights_kernel<decltype(rung)::value>), dim3(blocks), dim3(fc::kKnnThreads), 0, s, rowptr, cand, dist,
+                           (int)n_f, (int)n_slots, (int)k, (int)power, sel, weight);
+    });
+    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
 }  // extern "C"

@@ -8,9 +8,8 @@
 //                                  the running maximum m, s = sum exp(z - m), the target's logit and the plain sum of the logits
 //                                  (label smoothing); lc_finish_kernel merges the parts of a row IN PART ORDER, writes lse and the
 //                                  per-row loss and sums the rows in double in a fixed order (fc_loss.hip's scheme).
-//   fc_linear_topk                 lc_walk_kernel<1|2|4|8>: the same walk with a sorted list of the best (z, class) per row;
-//                                  lc_topk_merge_kernel merges the parts.  The order (z descending, class ascending; NaN after every
-//                                  number; empty slots last) is total, so the result cannot depend on parts.
+//   fc_linear_topk                 lc_walk_kernel<1|2|4|8>: the same walk with a sorted list of the best (z, class) per row (BestLogit,
+//                                  fc_select.hpp: why the result cannot depend on parts); parts_merge_kernel merges the parts.
 //   fc_linear_ce_backward_input    G = g_n (exp(z - lse_n) - q) recomputed tile by tile, g_h = G W accumulated in registers over ALL
 //                                  class tiles by the workgroup that owns the row tile: no partial sums.
 //   fc_linear_ce_backward_weight   the workgroup that owns a class tile accumulates g_W = G^T h and g_b = column sums of G over its
@@ -18,6 +17,7 @@
 // No atomics; every sum runs in a fixed order: two runs give the same bits.  Everything lives in caller-owned buffers.
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_select.hpp"
 #include "fc_workspace.hpp"
 
 namespace fc {
@@ -33,7 +33,6 @@ constexpr int kLcMaxParts = 64;
 constexpr int kLcMaxK = 8;
 constexpr int kLcTargetGroups = 1024;        // parts = 0: about four workgroups per CU ...
 constexpr int kLcMinTilesPerPart = 4;        // ... but no part shorter than four tiles
-constexpr int kLcNoClass = 0x7fffffff;
 constexpr int kLcSumThreads = 1024;
 constexpr int kLcSumWaves = kLcSumThreads / 64;
 
@@ -106,31 +105,6 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, const float m2, co
     m = mn;
 }
 
-// (z1, c1) before (z2, c2) in the prediction order: a real candidate before an empty slot, a number before a NaN, the larger logit
-// first, an exact tie to the lower class.
-__device__ __forceinline__ bool lc_before(float z1, int c1, float z2, int c2) {
-    if (c2 == kLcNoClass) return c1 != kLcNoClass;
-    if (c1 == kLcNoClass) return false;
-    const bool n1 = z1 != z1, n2 = z2 != z2;
-    if (n1 || n2) return n1 == n2 ? c1 < c2 : n2;
-    return z1 > z2 || (z1 == z2 && c1 < c2);
-}
-
-template <int KL>
-__device__ __forceinline__ void lc_list_insert(float (&z)[KL], int (&c)[KL], float nz, int nc) {
-    if (!lc_before(nz, nc, z[KL - 1], c[KL - 1])) return;
-    z[KL - 1] = nz;
-    c[KL - 1] = nc;
-#pragma unroll
-    for (int j = KL - 1; j > 0; --j) {
-        const bool sw = lc_before(z[j], c[j], z[j - 1], c[j - 1]);
-        const float zl = sw ? z[j] : z[j - 1], zh = sw ? z[j - 1] : z[j];
-        const int cl = sw ? c[j] : c[j - 1], ch = sw ? c[j - 1] : c[j];
-        z[j - 1] = zl, z[j] = zh;
-        c[j - 1] = cl, c[j] = ch;
-    }
-}
-
 // Workgroup (row tile, part).  Thread (row, q) = (tid / 4, tid % 4) reads classes 16 q .. 16 q + 15 of every tile of its row from
 // the tile in LDS, in class order; the four threads of a row are merged in q order, then (second launch) the parts in part order.
 // KL = 0: the loss statistics, float4 (m, s, z_target, sum z) at stat[part N + n].  KL > 0: the KL best, at (part N + n) k + j.
@@ -158,11 +132,7 @@ __global__ __launch_bounds__(kLcThreads) void lc_walk_kernel(const float* __rest
     float m = -INFINITY, s = 0.f, zt = 0.f, sz = 0.f;
     float lz[KA];
     int lc[KA];
-#pragma unroll
-    for (int j = 0; j < KA; ++j) {
-        lz[j] = -INFINITY;
-        lc[j] = kLcNoClass;
-    }
+    list_clear<BestLogit>(lz, lc);
     for (int t = t0; t < t1; ++t) {
         const int c0 = t * kLcTile;
         f32x4 acc[2][2];
@@ -198,7 +168,7 @@ __global__ __launch_bounds__(kLcThreads) void lc_walk_kernel(const float* __rest
         } else {
 #pragma unroll
             for (int u = 0; u < 16; ++u)
-                if (u < cnt) lc_list_insert<KA>(lz, lc, v[u], cbase + u);
+                if (u < cnt) list_insert<BestLogit>(lz, lc, v[u], cbase + u);
         }
     }
     if constexpr (KL == 0) {
@@ -223,7 +193,7 @@ __global__ __launch_bounds__(kLcThreads) void lc_walk_kernel(const float* __rest
         if (q == 0 && n < d.N) {
             for (int p = 1; p < 4; ++p)
 #pragma unroll
-                for (int j = 0; j < KA; ++j) lc_list_insert<KA>(lz, lc, Lz[row][p][j], Lc[row][p][j]);
+                for (int j = 0; j < KA; ++j) list_insert<BestLogit>(lz, lc, Lz[row][p][j], Lc[row][p][j]);
 #pragma unroll
             for (int j = 0; j < KA; ++j) {
                 if (j >= k) break;
@@ -233,18 +203,6 @@ __global__ __launch_bounds__(kLcThreads) void lc_walk_kernel(const float* __rest
             }
         }
     }
-}
-
-__device__ __forceinline__ double lc_block_sum(double v, double* slots) {
-#pragma unroll
-    for (int mk = 32; mk >= 1; mk >>= 1) v += __shfl_xor(v, mk, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kLcSumWaves; ++w) s += slots[w];
-    return s;
 }
 
 // One workgroup.  Thread t takes rows t, t + 1024, ...: the parts of a row merged in part order, lse and the row's loss written,
@@ -276,38 +234,12 @@ __global__ __launch_bounds__(kLcSumThreads) void lc_finish_kernel(const float4* 
         rows[n] = loss;
         sum += (double)loss;
     }
-    sum = lc_block_sum(sum, slots);
-    cnt = lc_block_sum(cnt, slots);
+    sum = block_sum<kLcSumWaves>(sum, slots);
+    cnt = block_sum<kLcSumWaves>(cnt, slots);
     if (threadIdx.x == 0) {
         total[0] = (float)sum;
         total[1] = (float)(sum / cnt);
         total[2] = (float)cnt;
-    }
-}
-
-template <int KL>
-__global__ __launch_bounds__(256) void lc_topk_merge_kernel(const float* __restrict__ wsZ, const int* __restrict__ wsC, const int N,
-                                                            const int k, const int parts, int64_t* __restrict__ idx,
-                                                            float* __restrict__ z) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    float lz[KL];
-    int lc[KL];
-#pragma unroll
-    for (int j = 0; j < KL; ++j) {
-        lz[j] = -INFINITY;
-        lc[j] = kLcNoClass;
-    }
-    for (int p = 0; p < parts; ++p)
-        for (int j = 0; j < k; ++j) {
-            const size_t e = ((size_t)p * N + n) * k + j;
-            lc_list_insert<KL>(lz, lc, wsZ[e], wsC[e]);
-        }
-#pragma unroll
-    for (int j = 0; j < KL; ++j) {
-        if (j >= k) break;
-        idx[(size_t)n * k + j] = lc[j] == kLcNoClass ? -1 : lc[j];
-        z[(size_t)n * k + j] = lc[j] == kLcNoClass ? -INFINITY : lz[j];
     }
 }
 
@@ -492,16 +424,9 @@ namespace {
 
 int lc_tiles(int n) { return (n + fc::kLcTile - 1) / fc::kLcTile; }
 
-// parts = 0: the most parts the library may choose when `own` tiles each own a workgroup (what the workspace query sizes for)
-int lc_parts_cap(int own) {
-    const int p = fc::kLcTargetGroups / own;
-    return p < 1 ? 1 : (p > fc::kLcMaxParts ? fc::kLcMaxParts : p);
-}
-
-// ... and what it chooses: no part shorter than kLcMinTilesPerPart of the `walk` tiles
-int lc_parts_auto(int own, int walk) {
-    const int by_range = (walk + fc::kLcMinTilesPerPart - 1) / fc::kLcMinTilesPerPart;
-    return lc_parts_cap(own) < by_range ? lc_parts_cap(own) : by_range;
+// parts = 0 when the tiles of `own` rows or classes each own a workgroup and walk the tiles of `walk` (fc_select.hpp)
+int lc_choose_parts(int own, int walk) {
+    return fc::parts_auto(lc_tiles(own), lc_tiles(walk), fc::kLcTargetGroups, fc::kLcMaxParts, fc::kLcMinTilesPerPart);
 }
 
 bool lc_dims_ok(int32_t N, int32_t H, int32_t K) {
@@ -534,7 +459,7 @@ extern "C" {
 size_t fc_linear_ce_workspace_bytes(int32_t N, int32_t H, int32_t K, int32_t parts, int32_t pass, int32_t k) {
     if (!lc_dims_ok(N, H, K) || !lc_parts_ok(parts)) return 0;
     if (pass == 2 && (k < 1 || k > fc::kLcMaxK)) return 0;
-    const int p = parts == 0 ? lc_parts_cap(lc_tiles(pass == 1 ? K : N)) : parts;
+    const int p = parts == 0 ? fc::parts_cap(lc_tiles(pass == 1 ? K : N), fc::kLcTargetGroups, fc::kLcMaxParts) : parts;
     if (pass == 0) return fc::carved_bytes(lc_forward_ws, p, N);
     if (pass == 1) return fc::carved_bytes(lc_weight_ws, p, K, H);            /* backward, weight side */
     return pass == 2 ? fc::carved_bytes(lc_topk_ws, p, N, k) : 0;
@@ -545,7 +470,7 @@ int fc_linear_ce_forward(const float* h, const float* weight, const float* bias,
                          float* total, void* workspace, size_t workspace_bytes, void* stream) {
     if (!lc_dims_ok(N, H, K) || !lc_parts_ok(parts) || !h || !weight || !target || !lse || !loss_rows || !total) return FC_ERR_BAD_ARGUMENT;
     if (!workspace || workspace_bytes < fc_linear_ce_workspace_bytes(N, H, K, parts, 0, 0)) return FC_ERR_WORKSPACE;
-    if (parts == 0) parts = lc_parts_auto(lc_tiles(N), lc_tiles(K));
+    if (parts == 0) parts = lc_choose_parts(N, K);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const fc::LcDims d{N, H, K};
     fc::Carver ws(workspace);
@@ -561,23 +486,18 @@ int fc_linear_topk(const float* h, const float* weight, const float* bias, int32
                    int64_t* idx, float* z, void* workspace, size_t workspace_bytes, void* stream) {
     if (!lc_dims_ok(N, H, K) || !lc_parts_ok(parts) || !h || !weight || !idx || !z || k < 1 || k > fc::kLcMaxK) return FC_ERR_BAD_ARGUMENT;
     if (!workspace || workspace_bytes < fc_linear_ce_workspace_bytes(N, H, K, parts, 2, k)) return FC_ERR_WORKSPACE;
-    if (parts == 0) parts = lc_parts_auto(lc_tiles(N), lc_tiles(K));
+    if (parts == 0) parts = lc_choose_parts(N, K);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const fc::LcDims d{N, H, K};
     fc::Carver ws(workspace);
     const LcTopkWs w = lc_topk_ws(ws, parts, N, k);
-    const dim3 grid((unsigned)lc_tiles(N), (unsigned)parts), merge((unsigned)((N + 255) / 256));
-#define FC_LC_TOPK(KL)                                                                                                                  \
-    do {                                                                                                                                \
-        hipLaunchKernelGGL(fc::lc_walk_kernel<KL>, grid, dim3(fc::kLcThreads), 0, s, h, weight, bias, (const int64_t*)nullptr, d, parts, \
-                           (float4*)nullptr, w.z, w.cls, k);                                                                            \
-        hipLaunchKernelGGL(fc::lc_topk_merge_kernel<KL>, merge, dim3(256), 0, s, w.z, w.cls, N, k, parts, idx, z);                      \
-    } while (0)
-    if (k == 1) FC_LC_TOPK(1);
-    else if (k == 2) FC_LC_TOPK(2);
-    else if (k <= 4) FC_LC_TOPK(4);
-    else FC_LC_TOPK(8);
-#undef FC_LC_TOPK
+    const dim3 grid((unsigned)lc_tiles(N), (unsigned)parts);
+    fc::dispatch_k<1, 2, 4, 8>(k, [&](auto rung) {
+        constexpr int KL = decltype(rung)::value;
+        hipLaunchKernelGGL(fc::lc_walk_kernel<KL>, grid, dim3(fc::kLcThreads), 0, s, h, weight, bias, (const int64_t*)nullptr, d, parts,
+                           (float4*)nullptr, w.z, w.cls, k);
+        fc::launch_parts_merge<fc::BestLogit, KL>(w.z, w.cls, N, k, parts, idx, z, s);
+    });
     return lc_status();
 }
 
@@ -599,7 +519,7 @@ int fc_linear_ce_backward_weight(const float* h, const float* weight, const floa
         return FC_ERR_BAD_ARGUMENT;
     const size_t need = fc_linear_ce_workspace_bytes(N, H, K, parts, 1, 0);
     if (need && (!workspace || workspace_bytes < need)) return FC_ERR_WORKSPACE;
-    if (parts == 0) parts = lc_parts_auto(lc_tiles(K), lc_tiles(N));
+    if (parts == 0) parts = lc_choose_parts(K, N);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const fc::LcDims d{N, H, K};
     const size_t nW = (size_t)K * H;

@@ -20,24 +20,6 @@ constexpr int kGradThreads = 256;
 constexpr int kDenseMaxThr = 16;
 constexpr int kDenseMaxGrid = 2048;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// Sum over a kLossThreads workgroup, valid in thread 0: xor tree inside each wavefront, then the wavefronts in index order.
-__device__ __forceinline__ double block_sum(double v, double* slots) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kLossWaves; ++w) s += slots[w];
-    return s;
-}
-
 // out = sum(partials[2g]) / den0 + sum(partials[2g+1]) / den1 over g < G.  One workgroup: thread t takes g = t, t + 1024, ...
 template <typename T>
 __global__ __launch_bounds__(kLossThreads) void final_sum_kernel(const double* __restrict__ partials, int G, double den0, double den1,
@@ -48,8 +30,8 @@ __global__ __launch_bounds__(kLossThreads) void final_sum_kernel(const double* _
         s0 += partials[2 * (size_t)g];
         s1 += partials[2 * (size_t)g + 1];
     }
-    s0 = block_sum(s0, slots);
-    s1 = block_sum(s1, slots);
+    s0 = block_sum<kLossWaves>(s0, slots);
+    s1 = block_sum<kLossWaves>(s1, slots);
     if (threadIdx.x == 0) out[0] = static_cast<T>(s0 / den0 + s1 / den1);
 }
 
@@ -91,8 +73,8 @@ __global__ __launch_bounds__(kLossThreads) void twin_forward_kernel(const T* __r
             sn = (double)(y * d + rest * relu_keep_nan(mu - d));
         }
     }
-    sp = block_sum(sp, slots);
-    sn = block_sum(sn, slots);
+    sp = block_sum<kLossWaves>(sp, slots);
+    sn = block_sum<kLossWaves>(sn, slots);
     if (threadIdx.x == 0) {
         if (gridDim.x == 1) {
             loss[0] = static_cast<T>(sp / (double)P + sn / (double)M);
@@ -293,7 +275,7 @@ __global__ __launch_bounds__(kLossThreads) void label_smoothing_forward_kernel(c
         ls_row_stats<T, G>(pred + (size_t)n * K, K, target[n], weight, conf, off, l, mx, se, stw, stwx);
         if (l == 0) v = (double)(t_log<T>(se) * stw - stwx);
     }
-    v = block_sum(v, slots);
+    v = block_sum<kLossWaves>(v, slots);
     if (threadIdx.x == 0) {
         if (gridDim.x == 1) {
             loss[0] = static_cast<T>(v / (double)N);

@@ -2,24 +2,17 @@
 //   fc_match_topk     the dense 64 x 64 x 16-channel LDS tile of fc_twin_count_dense (fc_pair.hpp) with a selection on top of it;
 //                     the N_T x N_S matrix never exists.
 // d2 is fc_pair.hpp's distance, so a match agrees bit for bit with fc_pair_sqdist and with the counts of fc_twin_count_dense.
-// Selection.  The order (d2, b) is TOTAL over the candidates of a row (b is unique), so "the k smallest" is one well-defined list
-// whatever the order in which candidates are looked at: every stage below keeps, of the candidates it has seen, the k smallest in
-// that order, and the k smallest of a union are the k smallest of the parts' k smallest.  Hence neither the lane that owns a
-// column, nor the split of the xS range over `parts` workgroups, nor the order of the merges can change a result, and an exact
-// tie goes to the lower row.  A NaN distance compares false with everything and is never kept.  No float atomics, no atomics at
-// all: two runs give the same bits.
+// Selection (fc_select.hpp: why no stage below can change a result): NearestRow lists, order (d2, b), so an exact tie goes to
+// the lower row and a NaN distance is never kept.
 //   lane      (ty, tx) of 16 x 16 owns rows 4 ty .. 4 ty + 3 of the xT tile and columns 4 tx .. 4 tx + 3 of every xS tile of its
-//             workgroup's range; it keeps a sorted list of K = 1, 2, 4 or 8 (>= k) entries per row in registers and inserts a
-//             pair only when it beats the list's last entry (rare once the list has warmed up).
-//   row       the sixteen tx lanes of a row sit next to each other in one wavefront: four xor-butterfly steps, each a bitonic
-//             merge of two sorted K-lists (mine against the partner's reversed: the K smaller of the pairwise comparison are the
-//             K smallest of the union and form a bitonic sequence, which log2 K compare-exchange stages sort).
+//             workgroup's range; it keeps a sorted list of K = 1, 2, 4 or 8 (>= k) entries per row in registers.
+//   row       the sixteen tx lanes of a row sit next to each other in one wavefront: four xor-butterfly steps (list_merge_xor).
 //   parts     workgroup (tile, p) searches the p-th share of the tile's xS range; with parts > 1 it leaves its list in the
-//             workspace and a second launch merges the lists of a row, one thread per row.
-// Empty slots hold (+inf, kNoRow) and are written out as d2 = +inf, idx = -1; an infinite distance of a real row still beats
-// them (lower b).
+//             workspace and a second launch (parts_merge_kernel) merges the lists of a row.
+// Empty slots are written out as d2 = +inf, idx = -1.
 #include "../../include/fieldconv_hip.h"
 #include "fc_pair.hpp"
+#include "fc_select.hpp"
 #include "fc_workspace.hpp"
 
 namespace fc {
@@ -28,67 +21,6 @@ constexpr int kMatchMaxK = 8;
 constexpr int kMatchMaxParts = 1024;
 constexpr int kMatchTargetGroups = 1024;     // parts = 0: enough workgroups for 4 per CU on 256 CUs ...
 constexpr int kMatchMinTilesPerPart = 4;     // ... but no part shorter than 4 tiles of xS (the row merge is paid once per part)
-constexpr int kNoRow = 0x7fffffff;
-
-// (d1, b1) before (d2, b2) in the selection order; false for a NaN d1
-template <typename T>
-__device__ __forceinline__ bool closer(T d1, int b1, T d2, int b2) {
-    return d1 < d2 || (d1 == d2 && b1 < b2);
-}
-
-template <typename T, int K>
-__device__ __forceinline__ void list_clear(T (&d)[K], int (&b)[K]) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        d[j] = static_cast<T>(INFINITY);
-        b[j] = kNoRow;
-    }
-}
-
-// Keep the K smallest of the sorted list and (nd, nb): the newcomer replaces the last entry and sinks to its place.
-template <typename T, int K>
-__device__ __forceinline__ void list_insert(T (&d)[K], int (&b)[K], T nd, int nb) {
-    if (!closer(nd, nb, d[K - 1], b[K - 1])) return;
-    d[K - 1] = nd;
-    b[K - 1] = nb;
-#pragma unroll
-    for (int j = K - 1; j > 0; --j) {
-        const bool sw = closer(d[j], b[j], d[j - 1], b[j - 1]);
-        const T dl = sw ? d[j] : d[j - 1], dh = sw ? d[j - 1] : d[j];
-        const int bl = sw ? b[j] : b[j - 1], bh = sw ? b[j - 1] : b[j];
-        d[j - 1] = dl, d[j] = dh;
-        b[j - 1] = bl, b[j] = bh;
-    }
-}
-
-// The K smallest of this lane's sorted list and the sorted list of lane ^ mask, sorted, the same in both lanes.
-template <typename T, int K>
-__device__ __forceinline__ void list_merge_xor(T (&d)[K], int (&b)[K], int mask) {
-    T od[K];
-    int ob[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        od[j] = __shfl_xor(d[K - 1 - j], mask, 64);
-        ob[j] = __shfl_xor(b[K - 1 - j], mask, 64);
-    }
-#pragma unroll
-    for (int j = 0; j < K; ++j)
-        if (closer(od[j], ob[j], d[j], b[j])) {
-            d[j] = od[j];
-            b[j] = ob[j];
-        }
-#pragma unroll
-    for (int s = K / 2; s >= 1; s >>= 1)
-#pragma unroll
-        for (int j = 0; j < K; ++j)
-            if ((j & s) == 0) {
-                const bool sw = closer(d[j + s], b[j + s], d[j], b[j]);
-                const T dl = sw ? d[j + s] : d[j], dh = sw ? d[j] : d[j + s];
-                const int bl = sw ? b[j + s] : b[j], bh = sw ? b[j] : b[j + s];
-                d[j] = dl, d[j + s] = dh;
-                b[j] = bl, b[j + s] = bh;
-            }
-}
 
 // ptr entry m clamped to [0, N]: a malformed table can give a meaningless result, never an access outside the features
 __device__ __forceinline__ int segment_bound(const int64_t* __restrict__ ptr, int m, int N) {
@@ -129,11 +61,12 @@ __global__ __launch_bounds__(kDenseThreads) void match_tile_kernel(const T* __re
     const int tilesS = (hiS - s0 + kDenseTile - 1) / kDenseTile, per = (tilesS + parts - 1) / parts;
     const int t0 = min(part * per, tilesS), t1 = min(t0 + per, tilesS);
 
+    using Row = NearestRow<T>;
     T bd[4][K];
     int bb[4][K], excl[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        list_clear(bd[i], bb[i]);
+        list_clear<Row>(bd[i], bb[i]);
         const int a = a0 + 4 * ty + i;
         const int64_t e = (exclude && a < hiT) ? exclude[a] : -1;
         excl[i] = (e >= 0 && e < nS) ? (int)e : -1;
@@ -182,14 +115,14 @@ __global__ __launch_bounds__(kDenseThreads) void match_tile_kernel(const T* __re
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int b = b0 + 4 * tx + j;
-                if (b < hiS && b != excl[i]) list_insert(bd[i], bb[i], acc[i][j], b);
+                if (b < hiS && b != excl[i]) list_insert<Row>(bd[i], bb[i], acc[i][j], b);
             }
     }
     // the sixteen lanes of a row: lanes 16 q .. 16 q + 15 of the wavefront, so xor 1, 2, 4, 8 stays inside the row
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int m = 1; m < 16; m <<= 1) list_merge_xor(bd[i], bb[i], m);
+        for (int m = 1; m < 16; m <<= 1) list_merge_xor<Row>(bd[i], bb[i], m);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int a = a0 + 4 * ty + i;
@@ -198,7 +131,7 @@ __global__ __launch_bounds__(kDenseThreads) void match_tile_kernel(const T* __re
         for (int j = 0; j < K; ++j) {
             if (j >= k) break;
             if (FINAL) {
-                idx[(size_t)a * k + j] = bb[i][j] == kNoRow ? -1 : bb[i][j];
+                idx[(size_t)a * k + j] = bb[i][j] == kSelNone ? -1 : bb[i][j];
                 d2[(size_t)a * k + j] = bd[i][j];
             } else {
                 const size_t e = ((size_t)part * nT + a) * k + j;
@@ -209,39 +142,14 @@ __global__ __launch_bounds__(kDenseThreads) void match_tile_kernel(const T* __re
     }
 }
 
-// One thread per row of xT: the k smallest of its parts' lists.
-template <typename T, int K>
-__global__ __launch_bounds__(256) void match_merge_kernel(const T* __restrict__ wsD, const int* __restrict__ wsI, int nT, int k, int parts,
-                                                          int64_t* __restrict__ idx, T* __restrict__ d2) {
-    const int a = blockIdx.x * 256 + threadIdx.x;
-    if (a >= nT) return;
-    T bd[K];
-    int bb[K];
-    list_clear(bd, bb);
-    for (int p = 0; p < parts; ++p)
-        for (int j = 0; j < k; ++j) {
-            const size_t e = ((size_t)p * nT + a) * k + j;
-            list_insert(bd, bb, wsD[e], wsI[e]);
-        }
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        if (j >= k) break;
-        idx[(size_t)a * k + j] = bb[j] == kNoRow ? -1 : bb[j];
-        d2[(size_t)a * k + j] = bd[j];
-    }
-}
-
 }  // namespace fc
 
 namespace {
 
 int tiles_of(int n) { return (n + fc::kDenseTile - 1) / fc::kDenseTile; }
 
-// parts = 0: the most parts the library may choose for N_T rows (what the workspace query sizes for)
-int auto_parts_cap(int32_t nT) {
-    const int p = fc::kMatchTargetGroups / tiles_of(nT);
-    return p < 1 ? 1 : (p > fc::kMatchMaxParts ? fc::kMatchMaxParts : p);
-}
+// parts = 0: as many parts as fill the card, none shorter than kMatchMinTilesPerPart tiles of xS; the workspace query sizes for the cap
+int match_parts_cap(int32_t nT) { return fc::parts_cap(tiles_of(nT), fc::kMatchTargetGroups, fc::kMatchMaxParts); }
 
 // [d2: parts N_T k entries of the dtype][idx: parts N_T k int32]; the query sizes it for 8-byte distances
 template <typename T>
@@ -259,23 +167,19 @@ int match_topk(const void* xS, int32_t nS, const void* xT, int32_t nT, int32_t C
     fc::Carver c(ws);
     const MatchWs<T> w = match_ws<T>(c, nT, k, parts);
     const dim3 grid((unsigned)(ptrT ? nT / fc::kDenseTile + B : tiles_of(nT)), (unsigned)parts);
-#define FC_MATCH(K)                                                                                                                      \
-    do {                                                                                                                                 \
-        if (parts == 1)                                                                                                                  \
-            hipLaunchKernelGGL((fc::match_tile_kernel<T, K, true>), grid, dim3(fc::kDenseThreads), 0, s, static_cast<const T*>(xS), nS,  \
-                               static_cast<const T*>(xT), nT, C, ptrS, ptrT, B, exclude, k, parts, idx, static_cast<T*>(d2), w.d2, w.idx); \
-        else {                                                                                                                           \
-            hipLaunchKernelGGL((fc::match_tile_kernel<T, K, false>), grid, dim3(fc::kDenseThreads), 0, s, static_cast<const T*>(xS), nS, \
-                               static_cast<const T*>(xT), nT, C, ptrS, ptrT, B, exclude, k, parts, idx, static_cast<T*>(d2), w.d2, w.idx); \
-            hipLaunchKernelGGL((fc::match_merge_kernel<T, K>), dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, s, w.d2, w.idx, nT, k, \
-                               parts, idx, static_cast<T*>(d2));                                                                         \
-        }                                                                                                                                \
-    } while (0)
-    if (k == 1) FC_MATCH(1);
-    else if (k == 2) FC_MATCH(2);
-    else if (k <= 4) FC_MATCH(4);
-    else FC_MATCH(8);
-#undef FC_MATCH
+    const T *pS = static_cast<const T*>(xS), *pT = static_cast<const T*>(xT);
+    T* out = static_cast<T*>(d2);
+    fc::dispatch_k<1, 2, 4, 8>(k, [&](auto rung) {
+        constexpr int K = decltype(rung)::value;
+        if (parts == 1) {
+            hipLaunchKernelGGL((fc::match_tile_kernel<T, K, true>), grid, dim3(fc::kDenseThreads), 0, s, pS, nS, pT, nT, C, ptrS, ptrT, B, exclude,
+                               k, parts, idx, out, w.d2, w.idx);
+        } else {
+            hipLaunchKernelGGL((fc::match_tile_kernel<T, K, false>), grid, dim3(fc::kDenseThreads), 0, s, pS, nS, pT, nT, C, ptrS, ptrT, B, exclude,
+                               k, parts, idx, out, w.d2, w.idx);
+            fc::launch_parts_merge<fc::NearestRow<T>, K>(w.d2, w.idx, nT, k, parts, idx, out, s);
+        }
+    });
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
@@ -285,7 +189,7 @@ extern "C" {
 
 size_t fc_match_workspace_bytes(int32_t N_T, int32_t k, int32_t parts) {
     if (N_T < 1 || k < 1 || k > fc::kMatchMaxK || parts < 0 || parts > fc::kMatchMaxParts) return 0;
-    return fc::carved_bytes(match_ws<double>, N_T, k, parts == 0 ? auto_parts_cap(N_T) : parts);
+    return fc::carved_bytes(match_ws<double>, N_T, k, parts == 0 ? match_parts_cap(N_T) : parts);
 }
 
 int fc_match_topk(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int32_t C, int32_t dtype, const int64_t* ptr_S,
@@ -297,10 +201,7 @@ int fc_match_topk(const void* xS, int32_t N_S, const void* xT, int32_t N_T, int3
     if (ptr_T && (B < 1 || (int64_t)N_T + (int64_t)fc::kDenseTile * B >= ((int64_t)1 << 31))) return FC_ERR_BAD_ARGUMENT;
     const size_t need = fc_match_workspace_bytes(N_T, k, parts);
     if (need && (!workspace || workspace_bytes < need)) return FC_ERR_WORKSPACE;
-    if (parts == 0) {          // as many parts as fill the card, none shorter than kMatchMinTilesPerPart tiles of xS
-        const int by_range = (tiles_of(N_S) + fc::kMatchMinTilesPerPart - 1) / fc::kMatchMinTilesPerPart;
-        parts = auto_parts_cap(N_T) < by_range ? auto_parts_cap(N_T) : by_range;
-    }
+    if (parts == 0) parts = fc::parts_auto(tiles_of(N_T), tiles_of(N_S), fc::kMatchTargetGroups, fc::kMatchMaxParts, fc::kMatchMinTilesPerPart);
     hipStream_t s = static_cast<hipStream_t>(stream);
     return dtype == 0 ? match_topk<float>(xS, N_S, xT, N_T, C, ptr_S, ptr_T, B, exclude, k, parts, idx, d2, workspace, s)
                       : match_topk<double>(xS, N_S, xT, N_T, C, ptr_S, ptr_T, B, exclude, k, parts, idx, d2, workspace, s);

@@ -211,6 +211,20 @@ def test_topk_equals_restatement_on_the_kernels_logits(dev, shape, parts):
     assert np.array_equal(rows[ok].view(np.uint32), want.astype(np.float32).view(np.uint32))
 
 
+@pytest.mark.parametrize('parts', [1, 3])
+@pytest.mark.parametrize('k', [1, 2, 3, 4, 5, 8])
+def test_topk_every_rung_of_the_list_ladder(dev, k, parts):
+    """Every list length the kernels are compiled for (1, 2, 4, 8), filled (k = K) and not (k = 3, 5), from one part and merged
+    from three.  65 rows and 130 classes: a second row tile, and three class tiles, so that each of three parts has one."""
+    from fieldconv_amd.functional import linear_topk
+    N, H, K = 65, 33, 130
+    h, W, b, _, _ = inputs(N, H, K)
+    idx, zk = linear_topk(D(h, dev), D(W, dev), D(b, dev), k, parts)
+    want_idx, want_z = href.topk(kernel_logits(N, H, K), k)
+    assert np.array_equal(Hn(idx), want_idx)
+    assert np.array_equal(Hn(zk).view(np.uint32), want_z.view(np.uint32))
+
+
 def test_equal_logits_nan_logits_and_bad_targets(dev):
     from fieldconv_amd.functional import linear_cross_entropy, linear_topk
     N, H, K = 70, 9, 130

@@ -120,6 +120,18 @@ def test_result_does_not_depend_on_parts(dev, ndt, dt):
     assert same(match_descriptors(T(xS, dev), T(xT, dev), k=3, parts=7), mref.topk(xS, xT, 3))
 
 
+@pytest.mark.parametrize('ndt,dt', DTYPES, ids=['f32', 'f64'])
+@pytest.mark.parametrize('parts', [1, 3])
+@pytest.mark.parametrize('k', [1, 2, 3, 4, 5, 8])
+def test_every_rung_of_the_list_ladder(dev, k, parts, ndt, dt):
+    """Every list length the kernels are compiled for (1, 2, 4, 8), filled (k = K) and not (k = 3, 5), from one part and merged
+    from three.  65 rows of xT: a second tile; 130 rows of xS: three tiles, so that each of three parts has one."""
+    from fieldconv_amd.functional import match_descriptors
+    xS, xT = features(65, 130, 5, seed=21, ndt=ndt)
+    xS[[64, 129]] = xS[2]          # exact ties across the parts' ranges
+    assert same(match_descriptors(T(xS, dev), T(xT, dev), k=k, parts=parts), mref.topk(xS, xT, k))
+
+
 # ------------------------------------------------------------------ segments (the meshes of two mini-batches)
 @pytest.mark.parametrize('ndt,dt', DTYPES, ids=['f32', 'f64'])
 def test_segments(dev, ndt, dt):
