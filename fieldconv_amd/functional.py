@@ -4,12 +4,12 @@ The tensors are plain torch device buffers; only raw pointers, sizes and the cur
 cross into libfieldconv_hip.so (include/fieldconv_hip.h).
 """
 import ctypes
-import math
 import os
 
 import torch
 
 from . import _lib
+from ._launch import NO_GUARD as _NO_GUARD, _dp, _p, _po, carve as _carve, on as _on, scratch as _scratch, stream as _stream          # noqa: F401  (blocks.py and the tests reach them as Fn._*)
 from ._lib import FcCsr, FcDims, FcEpilogue, FcFilterParams, check
 
 
@@ -80,50 +80,6 @@ def on_device(t):
     return t.is_cuda
 
 
-_raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-_cur_device = getattr(torch._C, '_cuda_getDevice', None)
-
-
-def _stream():
-    """The current HIP stream of the current device as a raw pointer.  torch.cuda.current_stream() costs ~10 us of
-    Python per call -- with ~25 launches per network forward that was a quarter of the host's enqueue time."""
-    if _raw_stream is not None and _cur_device is not None:
-        return ctypes.c_void_p(_raw_stream(_cur_device()))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class _NoGuard:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NO_GUARD = _NoGuard()
-
-
-def _on(device):
-    """Device guard for the launches below; free when `device` already is the current one (the usual case)."""
-    if _cur_device is not None and device.index is not None and _cur_device() == device.index:
-        return _NO_GUARD
-    return torch.cuda.device(device)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _dp(t):
-    """data pointer of an optional tensor (None: NULL) for a struct field"""
-    return t.data_ptr() if t is not None else None
-
-
-def _po(t):
-    """_p of an optional tensor (None: NULL)"""
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _csr(rowptr, nbr, runs=None):
     return FcCsr(rowptr.data_ptr(), nbr.data_ptr() if nbr.numel() else None, _dp(runs))
 
@@ -145,37 +101,6 @@ def _records(graph):
     if graph.factored:
         return 1, graph.rec_t, graph.rec_s
     return 0, graph.sten_t, graph.sten_s
-
-
-def _scratch(nbytes, device, floor=0):
-    """Device scratch of `nbytes` bytes (uint8), the ONE place workspaces are allocated.  What a zero-byte request gives follows the
-    entry point: floor=0 an empty tensor (its pointer is NULL), floor=1 a live one-byte buffer (the block-level entry points),
-    floor=None no tensor at all (fc_forward_*, fc_cgemm: _po(None) is NULL)."""
-    if floor is None:
-        if not nbytes:
-            return None
-        floor = 0
-    return torch.empty(max(int(nbytes), floor), dtype=torch.uint8, device=device)
-
-
-def _carve(shapes, device, zero=False, extra=None):
-    """One flat float32 buffer and a view of it per shape, pieces 16-byte aligned (None entries stay None and take no room); with
-    `extra`, that many floats behind the pieces come last, flat.  Everything returned shares ONE storage."""
-    counts = [math.prod(shp) for shp in shapes if shp is not None]
-    sizes = [(n + 3) // 4 * 4 for n in counts]
-    flat = (torch.zeros if zero else torch.empty)(sum(sizes) + (extra or 0), dtype=torch.float32, device=device)
-    parts = iter(flat.split(sizes if extra is None else sizes + [extra]))
-    counts = iter(counts)
-    out = []
-    for shp in shapes:
-        if shp is None:
-            out.append(None)
-        else:
-            n = next(counts)
-            out.append(next(parts)[:n].view(shp) if n % 4 else next(parts).view(shp))
-    if extra is not None:
-        out.append(next(parts))
-    return out
 
 
 def _edge_split():

@@ -9,11 +9,10 @@ Dijkstra with float32 additions gives the same numbers, tests/_geodesic_ref.py),
 pos (V,3) float32, face (3,F) int64 (the PyG layout), on a ROCm device or on the host: the arithmetic runs on the device
 either way and results go back to pos's device, as in transforms.SupportGraph.  There is no CPU arithmetic path.  Bad
 arguments raise ValueError before anything is launched.  Nothing here is differentiable."""
-import ctypes
-
 import torch
 
 from . import _lib
+from ._launch import device_of as _device_of, on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
 from .pooling import check_ptr, ptr_on
 
 # Vertices of one mesh solved in LDS by every solver of the family (fc_geodesic_lds_vertices: 8 B per vertex of the CU's 160 KiB
@@ -22,22 +21,6 @@ from .pooling import check_ptr, ptr_on
 LDS_VERTICES = 20000
 _ROW_CHUNK_FLOATS = 1 << 26          # distance rows per launch: at most 256 MiB of them
 _WORKSPACE_BYTES = 1 << 28           # queries per launch where they need workspace slots: at most 256 MiB of them
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _device_of(pos):
-    if pos.is_cuda:
-        return pos.device
-    if not torch.cuda.is_available():
-        raise RuntimeError('fieldconv_amd geodesics are computed on a ROCm device and none is visible; there is no CPU path')
-    return torch.device('cuda', torch.cuda.current_device())
 
 
 def _check_mesh(pos, face, what):
@@ -144,8 +127,8 @@ def _check_diagonals(graph, diagonals, what):
 
 def _mesh_on(pos, face, what):
     """a checked mesh -> (pos, face) on the device, face's vertex numbers checked (one synchronisation), and the device"""
-    dev = _device_of(pos)
-    with torch.cuda.device(dev):
+    dev = _device_of(pos, 'geodesics')
+    with _on(dev):
         return pos.detach().to(dev).contiguous(), _face_on(face, int(pos.shape[0]), dev, what), dev
 
 
@@ -157,10 +140,10 @@ def _prepare(pos, face, graph, what, diagonals=False):
         raise ValueError(f'{what}: with diagonals a mesh has up to 9 directed edges per face, and edges are 32-bit indices in the kernels')
     if graph is None:
         p, f, dev = _mesh_on(pos, face, what)
-        with torch.cuda.device(dev):
+        with _on(dev):
             return p, f, _edge_graph(p, f, dev, diagonals), dev
-    dev = _device_of(pos)
-    with torch.cuda.device(dev):
+    dev = _device_of(pos, 'geodesics')
+    with _on(dev):
         return pos.detach().to(dev).contiguous(), None, _graph_on(graph, int(pos.shape[0]), dev, what), dev
 
 
@@ -168,9 +151,7 @@ def _rows_per_call(rows_per_call, V, what):
     """the checked number of (V,) distance rows per launch; None: 256 MiB of them"""
     if rows_per_call is None:
         return max(1, _ROW_CHUNK_FLOATS // V)
-    if isinstance(rows_per_call, bool) or int(rows_per_call) != rows_per_call or rows_per_call < 1:
-        raise ValueError(f'{what}: rows_per_call must be an integer >= 1, got {rows_per_call!r}')
-    return int(rows_per_call)
+    return _whole(rows_per_call, 1, 2 ** 63 - 1, what, 'rows_per_call', integral_floats=True)
 
 
 def _batch_tables(pos_ptr, sample_ptr, V, S, what, name, sample_idx=None):
@@ -247,7 +228,7 @@ def geodesic_distances(pos, face, sources, graph=None, rows_per_call=None, retur
     lib = _lib.load()
     E = int(nbr.numel())
     out = torch.empty((S, V), dtype=torch.float32, device=pos.device)
-    with torch.cuda.device(dev):
+    with _on(dev):
         src = sources.detach().to(dev).contiguous()
         sweeps = torch.empty((S, 2), dtype=torch.int32, device=dev)
         for s0 in range(0, S, rows_per_call):
@@ -282,11 +263,11 @@ def nearest_sample(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=N
     p, _, (ptr, nbr, length), dev = _prepare(pos, face, graph, what, diagonals)
     lib = _lib.load()
     E = int(nbr.numel())
-    with torch.cuda.device(dev):
+    with _on(dev):
         src = sample_idx.detach().to(dev).contiguous()
         pp, sp = tables_on(dev)
         nbytes = lib.fc_geodesic_workspace_bytes(V, max_range)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws = _scratch(nbytes, dev, None)
         dist = torch.empty(V, dtype=torch.float32, device=dev)
         label = torch.empty(V, dtype=torch.int64, device=dev)
         sweeps = torch.empty((B, 2), dtype=torch.int32, device=dev)
@@ -350,7 +331,7 @@ def vertex_masses(pos, face):
     what = 'vertex_masses'
     _check_mesh(pos, face, what)
     p, f, dev = _mesh_on(pos, face, what)
-    with torch.cuda.device(dev):
+    with _on(dev):
         return _segment_sum(_face_areas(p, f, dev).repeat(3), f.reshape(-1), int(p.shape[0]), 3.0, dev).to(pos.device)
 
 
@@ -361,8 +342,8 @@ def sample_weights(pos, face, sample_idx, pos_ptr=None, sample_ptr=None, graph=N
     (label -1) contributes to nothing."""
     what = 'sample_weights'
     label, _ = nearest_sample(pos, face, sample_idx, pos_ptr, sample_ptr, graph, diagonals=diagonals)
-    dev = _device_of(pos)
-    with torch.cuda.device(dev):
+    dev = _device_of(pos, 'geodesics')
+    with _on(dev):
         mass = vertex_masses(pos, face).to(dev)
         w = _segment_sum(mass, label.to(dev), int(sample_idx.numel()), 1.0, dev)
     return w[:, None].to(pos.device)
@@ -373,7 +354,7 @@ def surface_area(pos, face):
     what = 'surface_area'
     _check_mesh(pos, face, what)
     p, f, dev = _mesh_on(pos, face, what)
-    with torch.cuda.device(dev):
+    with _on(dev):
         return float(_face_areas(p, f, dev).to(torch.float64).sum())
 
 
@@ -392,8 +373,8 @@ def geodesic_error(pos, face, pred, target, normalize=True, graph=None, rows_per
         raise ValueError(f'{what}: pred {tuple(pred.shape)} and target {tuple(target.shape)} must have the same length')
     if pred.device != target.device:
         raise ValueError(f'{what}: pred is on {pred.device}, target on {target.device}')
-    dev = _device_of(pos)
-    with torch.cuda.device(dev):
+    dev = _device_of(pos, 'geodesics')
+    with _on(dev):
         if graph is None:
             graph = _prepare(pos, face, None, what, diagonals)[2]
         uniq, inv = torch.unique(target.to(dev), return_inverse=True)

@@ -13,25 +13,9 @@ import torch
 
 from . import _lib
 from .geodesic import LDS_VERTICES          # noqa: F401  (the family's one LDS capacity, readable from here as well)
-from .geodesic import _batch_tables, _check_diagonals, _check_index, _check_mesh, _prepare, _ptr, _query_windows, _stream
-from .pooling import check_ptr, ptr_on
-
-
-def _int_in(value, lo, hi, what, name, where=''):
-    try:
-        ok = not isinstance(value, bool) and int(value) == value and lo <= int(value) <= hi
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f'{what}: {name}{where} must be an integer in [{lo}, {hi}], got {value!r}')
-    return int(value)
-
-
-def _per_mesh(value, B, what, name):
-    vals = list(value) if isinstance(value, (list, tuple)) or torch.is_tensor(value) else [value] * B
-    if len(vals) != B:
-        raise ValueError(f'{what}: {name} must be one integer or one per mesh ({B}), got {len(vals)}')
-    return vals
+from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
+from .geodesic import _batch_tables, _check_diagonals, _check_index, _check_mesh, _prepare, _query_windows
+from .pooling import check_ptr, per_mesh, ptr_on
 
 
 def _fps(pos, face, pos_ptr, host_ptr, S, starts, graph, what, diagonals=False):
@@ -44,11 +28,11 @@ def _fps(pos, face, pos_ptr, host_ptr, S, starts, graph, what, diagonals=False):
     out_ptr = [0]
     for s in S:
         out_ptr.append(out_ptr[-1] + s)
-    with torch.cuda.device(dev):
+    with _on(dev):
         tables = torch.tensor([S, starts, out_ptr[:-1]], dtype=torch.int64).to(dev)
         pp = None if host_ptr is None else ptr_on(pos_ptr, host_ptr, dev)
         nbytes = lib.fc_geodesic_fps_workspace_bytes(V, max_range)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws = _scratch(nbytes, dev, None)
         idx = torch.empty(out_ptr[-1], dtype=torch.int64, device=dev)
         dist = torch.empty(V, dtype=torch.float32, device=dev)
         sweeps = torch.empty(B, dtype=torch.int64, device=dev)
@@ -71,8 +55,8 @@ def geodesic_farthest_point_sample(pos, face, n_samples, start=0, graph=None, re
     _check_mesh(pos, face, what)
     _check_diagonals(graph, diagonals, what)
     V = int(pos.shape[0])
-    S = _int_in(n_samples, 1, V, what, 'n_samples')
-    st = _int_in(start, 0, V - 1, what, 'start')
+    S = _whole(n_samples, 1, V, what, 'n_samples', integral_floats=True)
+    st = _whole(start, 0, V - 1, what, 'start', integral_floats=True)
     idx, dist, sweeps = _fps(pos, face, None, None, [S], [st], graph, what, diagonals)
     out = (idx.to(pos.device),)
     if return_dist:
@@ -96,13 +80,13 @@ def geodesic_farthest_point_sample_batched(pos, face, pos_ptr, n_samples, start=
     _check_diagonals(graph, diagonals, what)
     host = check_ptr(pos_ptr, int(pos.shape[0]), what, 'pos_ptr')
     B = len(host) - 1
-    S, st = _per_mesh(n_samples, B, what, 'n_samples'), _per_mesh(start, B, what, 'start')
+    S, st = per_mesh(n_samples, B, what, 'n_samples'), per_mesh(start, B, what, 'start')
     for b in range(B):
         n_b = host[b + 1] - host[b]
         if n_b < 1:
             raise ValueError(f'{what}: mesh {b} holds no vertices')
-        S[b] = _int_in(S[b], 1, n_b, what, 'n_samples', f' of mesh {b}')
-        st[b] = _int_in(st[b], 0, n_b - 1, what, 'start', f' of mesh {b}')
+        S[b] = _whole(S[b], 1, n_b, what, 'n_samples', f' of mesh {b}', integral_floats=True)
+        st[b] = _whole(st[b], 0, n_b - 1, what, 'start', f' of mesh {b}', integral_floats=True)
     idx, dist, sweeps = _fps(pos, face, pos_ptr, host, S, st, graph, what, diagonals)
     out = (idx.to(pos.device),)
     if return_dist:
@@ -144,11 +128,11 @@ def geodesic_radius_edges(pos, face, sample_idx, epsilon, max_num_neighbors=512,
     lib = _lib.load()
     E_graph = int(nbr.numel())
     per_call, windows = _query_windows(S, lib.fc_geodesic_ball_workspace_bytes(max_range, 1))          # (no slots up to LDS_VERTICES)
-    with torch.cuda.device(dev):
+    with _on(dev):
         src = sample_idx.detach().to(dev).contiguous()
         pp, sp = tables_on(dev)
         nbytes = lib.fc_geodesic_ball_workspace_bytes(max_range, per_call)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws = _scratch(nbytes, dev, None)
         count = torch.empty(S, dtype=torch.int32, device=dev)
         for q0, nq in windows:
             _lib.check(lib.fc_geodesic_ball_count(_ptr(ptr), _ptr(nbr), _ptr(length), V, E_graph, _ptr(pp), _ptr(sp), B, max_range, _ptr(src),

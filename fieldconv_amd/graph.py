@@ -22,6 +22,8 @@ import os
 
 import torch
 
+from ._launch import _po, on as _on, scratch as _scratch, stream as _stream
+
 _CACHE_SIZE = 16        # meshes whose preprocessing is kept (a graph is ~100 B per edge)
 _cache = collections.OrderedDict()
 
@@ -104,7 +106,6 @@ def _native_build(supp_edges, sten, N, R, F, want_rec, want_geo):
     """fc_graph_build (csrc/fc_graph.hip) on device tensors: both edge groupings, ring-run offsets, slot -> edge
     permutations and -- with a stencil -- the factored / geometric records, plus the verdict flags (the one host
     synchronisation).  Returns a dict of tensors and 'flags' (int)."""
-    import ctypes
     from . import _lib
     lib = _lib.load()
     dev, E = supp_edges.device, int(supp_edges.shape[0])
@@ -112,7 +113,7 @@ def _native_build(supp_edges, sten, N, R, F, want_rec, want_geo):
     recf = (4 + 2 * F + 3) // 4 * 4
     i32 = dict(dtype=torch.int32, device=dev)
     out = {}
-    with torch.cuda.device(dev):
+    with _on(dev):
         for side in ('t', 's'):
             out['rowptr_' + side] = torch.empty(N + 1, **i32)
             out['nbr_' + side] = torch.empty(E, **i32)
@@ -126,12 +127,11 @@ def _native_build(supp_edges, sten, N, R, F, want_rec, want_geo):
                 out['geo_t'] = torch.zeros((E + 1024 // 32 + 16, 8), dtype=torch.float32, device=dev)
         flags = torch.empty(1, **i32)
         nbytes = lib.fc_graph_workspace_bytes(N, E, R, F, 1 if want_rec else 0)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(lib.fc_graph_build(p(edges), p(sten) if want_rec else None, N, E, R, F, p(out['rowptr_t']), p(out['nbr_t']),
-                                      p(out['runs_t']), p(out['perm_t']), p(out['rowptr_s']), p(out['nbr_s']), p(out['runs_s']),
-                                      p(out['perm_s']), p(out['rec_t']), p(out['rec_s']), p(out['geo_t']), p(flags), p(ws), nbytes,
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'fc_graph_build')
+        ws = _scratch(nbytes, dev)
+        _lib.check(lib.fc_graph_build(_po(edges), _po(sten) if want_rec else None, N, E, R, F, _po(out['rowptr_t']), _po(out['nbr_t']),
+                                      _po(out['runs_t']), _po(out['perm_t']), _po(out['rowptr_s']), _po(out['nbr_s']), _po(out['runs_s']),
+                                      _po(out['perm_s']), _po(out['rec_t']), _po(out['rec_s']), _po(out['geo_t']), _po(flags), _po(ws), nbytes,
+                                      _stream()), 'fc_graph_build')
         out['flags'] = int(flags.item())
     if out['flags'] & 4:
         raise IndexError(f'supp_edges refers to a vertex outside [0, {N})')

@@ -9,8 +9,8 @@ float32 only, contiguous tensors only; there is no CPU or eager path: a CPU tens
 import torch
 
 from . import _lib
-from .losses import _ptr, _stream
-from .matching import MAX_K, _whole
+from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
+from .matching import MAX_K
 
 MAX_PARTS = 64
 REDUCTIONS = ('none', 'mean', 'sum')
@@ -54,18 +54,14 @@ def _target(target, N, dev, what):
     return target.contiguous()
 
 
-def _workspace(lib, N, H, K, parts, which, k, dev):
-    nbytes = lib.fc_linear_ce_workspace_bytes(N, H, K, parts, which, k)
-    return (torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None), nbytes
-
-
 def _forward(h, weight, bias, target, conf, off, ignore_index, parts):
     """(lse (N), loss_rows (N), total (3): sum, mean, counted rows) of detached, checked operands"""
     lib = _lib.load()
     N, H, K = int(h.shape[0]), int(h.shape[1]), int(weight.shape[0])
     dev = h.device
-    with torch.cuda.device(dev):
-        ws, nbytes = _workspace(lib, N, H, K, parts, 0, 0, dev)
+    with _on(dev):
+        nbytes = lib.fc_linear_ce_workspace_bytes(N, H, K, parts, 0, 0)
+        ws = _scratch(nbytes, dev, None)
         lse = torch.empty(N, dtype=torch.float32, device=dev)
         rows = torch.empty(N, dtype=torch.float32, device=dev)
         total = torch.empty(3, dtype=torch.float32, device=dev)
@@ -92,7 +88,7 @@ class _LinearCrossEntropy(torch.autograd.Function):
         N, H, K = int(h.shape[0]), int(h.shape[1]), int(weight.shape[0])
         dev = h.device
         g_h = g_w = g_b = None
-        with torch.cuda.device(dev):
+        with _on(dev):
             g = g.detach().to(torch.float32)
             if reduction == 'none':
                 scale = g.contiguous()
@@ -103,7 +99,8 @@ class _LinearCrossEntropy(torch.autograd.Function):
                 _lib.check(lib.fc_linear_ce_backward_input(_ptr(h), _ptr(weight), _ptr(bias), _ptr(target), _ptr(lse), _ptr(scale), N, H, K,
                                                            conf, off, ignore_index, _ptr(g_h), _stream()), 'fc_linear_ce_backward_input')
             if need_w or need_b:
-                ws, nbytes = _workspace(lib, N, H, K, parts, 1, 0, dev)
+                nbytes = lib.fc_linear_ce_workspace_bytes(N, H, K, parts, 1, 0)
+                ws = _scratch(nbytes, dev, None)
                 g_w = torch.empty((K, H), dtype=torch.float32, device=dev) if need_w else None
                 g_b = torch.empty(K, dtype=torch.float32, device=dev) if need_b else None
                 _lib.check(lib.fc_linear_ce_backward_weight(_ptr(h), _ptr(weight), _ptr(bias), _ptr(target), _ptr(lse), _ptr(scale), N, H, K,
@@ -158,8 +155,9 @@ def linear_topk(h, weight, bias, k=1, parts=0):
     lib = _lib.load()
     dev = h.device
     hd, wd, bd = h.detach(), weight.detach(), None if bias is None else bias.detach()
-    with torch.cuda.device(dev):
-        ws, nbytes = _workspace(lib, N, H, K, parts, 2, k, dev)
+    with _on(dev):
+        nbytes = lib.fc_linear_ce_workspace_bytes(N, H, K, parts, 2, k)
+        ws = _scratch(nbytes, dev, None)
         idx = torch.empty((N, k), dtype=torch.int64, device=dev)
         z = torch.empty((N, k), dtype=torch.float32, device=dev)
         _lib.check(lib.fc_linear_topk(_ptr(hd), _ptr(wd), _ptr(bd), N, H, K, k, parts, _ptr(idx), _ptr(z), _ptr(ws), nbytes, _stream()),

@@ -18,7 +18,8 @@ import math
 import torch
 
 from . import _lib
-from .geodesic import _batch_tables, _check_diagonals, _check_index, _check_mesh, _face_on, _mesh_on, _prepare, _ptr, _query_windows, _stream
+from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
+from .geodesic import _batch_tables, _check_diagonals, _check_index, _check_mesh, _face_on, _mesh_on, _prepare, _query_windows
 
 # Reached vertices of one query whose tree state stays in LDS (fc_logmap_ball_lds_vertices: 36 B each, beside the 6 B per
 # vertex of the mesh's relaxation state); a larger ball keeps it in a workspace slot, with the same result.
@@ -49,7 +50,7 @@ def vertex_frames(pos, face):
     what = 'vertex_frames'
     _check_mesh(pos, face, what)
     p, f, dev = _mesh_on(pos, face, what)
-    with torch.cuda.device(dev):
+    with _on(dev):
         return tuple(t.to(pos.device) for t in _frames(p, f, dev))
 
 
@@ -103,10 +104,8 @@ def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_
     if R and (int(supp_edges.min()) < 0 or int(supp_edges.max()) >= S):
         raise ValueError(f'{what}: supp_edges must hold positions in sample_idx, in [0, {S})')
     bound = _check_bound(bound, what)
-    cap = BALL_LDS_VERTICES if ball_lds_vertices is None else ball_lds_vertices
-    if isinstance(cap, bool) or int(cap) != cap or not 0 <= cap <= BALL_LDS_VERTICES:
-        raise ValueError(f'{what}: ball_lds_vertices must be an integer in [0, {BALL_LDS_VERTICES}], got {ball_lds_vertices!r}')
-    cap = int(cap)
+    cap = BALL_LDS_VERTICES if ball_lds_vertices is None else _whole(ball_lds_vertices, 0, BALL_LDS_VERTICES, what, 'ball_lds_vertices',
+                                                                     integral_floats=True)
     if return_tree and S * V > _TREE_ENTRIES:
         raise ValueError(f'{what}: return_tree is for small cases, at most {_TREE_ENTRIES} (query, vertex) pairs, got {S} x {V}')
     B, max_range, _, _, tables_on = _batch_tables(pos_ptr, ptr, V, S, what, 'ptr', sample_idx)
@@ -117,7 +116,7 @@ def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_
                                         f'says {BALL_LDS_VERTICES}: they were built from different sources')
     E_graph = int(nbr.numel())
     per_call, windows = _query_windows(S, lib.fc_logmap_workspace_bytes(max_range, 1, cap))
-    with torch.cuda.device(dev):
+    with _on(dev):
         nrm, e1, e2 = _frames(p, _face_on(face, V, dev, what) if f is None else f, dev)          # (f is None: graph= was given)
         src = sample_idx.detach().to(dev).contiguous()
         rows = supp_edges.detach().to(dev)
@@ -126,7 +125,7 @@ def log_map_transport(pos, face, sample_idx, supp_edges, bound, graph=None, pos_
         target = rows[order.indices, 1].contiguous()
         pp, sp = tables_on(dev)
         nbytes = lib.fc_logmap_workspace_bytes(max_range, per_call, cap)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws = _scratch(nbytes, dev, None)
         mag = torch.empty(R, dtype=torch.float32, device=dev)
         ang = torch.empty(R, dtype=torch.float32, device=dev)
         xp = torch.empty((R, 2), dtype=torch.float32, device=dev)

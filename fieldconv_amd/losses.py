@@ -9,17 +9,10 @@ import ctypes
 import torch
 
 from . import _lib
+from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
 
 _DTYPES = {torch.float32: 0, torch.float64: 1}
 MAX_THRESHOLDS = 16
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _features(xS, xT, what):
@@ -58,7 +51,7 @@ def _sqdist_unchecked(xS, xT, pairs):
     lib = _lib.load()
     K = int(pairs.shape[0])
     d2 = torch.empty(K, dtype=xS.dtype, device=xS.device)
-    with torch.cuda.device(xS.device):
+    with _on(xS.device):
         _lib.check(lib.fc_pair_sqdist(_ptr(xS), xS.shape[0], _ptr(xT), xT.shape[0], xS.shape[1], _DTYPES[xS.dtype], _ptr(pairs), K,
                                       _ptr(d2), _stream()), 'fc_pair_sqdist')
     return d2
@@ -89,9 +82,9 @@ class _TwinLoss(torch.autograd.Function):
         xSc, xTc = xS.detach().contiguous(), xT.detach().contiguous()
         P, M = int(p_.shape[0]), int(n_.shape[0])
         dev, dt = xS.device, xS.dtype
-        with torch.cuda.device(dev):
+        with _on(dev):
             nbytes = lib.fc_twin_loss_workspace_bytes(P, M)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = _scratch(nbytes, dev)
             d2 = torch.empty(P + M, dtype=dt, device=dev)
             loss = torch.empty(1, dtype=dt, device=dev)
             _lib.check(lib.fc_twin_loss_forward(_ptr(xSc), xSc.shape[0], _ptr(xTc), xTc.shape[0], xSc.shape[1], _DTYPES[dt], _ptr(p_), P,
@@ -107,7 +100,7 @@ class _TwinLoss(torch.autograd.Function):
         xS, xT, p_, n_, yN, d2 = ctx.saved_tensors
         P, M = int(p_.shape[0]), int(n_.shape[0])
         dev, dt = xS.device, xS.dtype
-        with torch.cuda.device(dev):
+        with _on(dev):
             # the pairs at each row, in list order (torch's stable sort on the device; nothing comes back to the host)
             rows = torch.cat((p_, n_), 0)
             rowptr_T, order_T = _row_segments(rows[:, 0].contiguous(), xT.shape[0])
@@ -150,7 +143,7 @@ def twin_count_dense(xS, xT, thresholds):
     lib = _lib.load()
     xSc, xTc = xS.detach().contiguous(), xT.detach().contiguous()
     T = len(thr)
-    with torch.cuda.device(xS.device):
+    with _on(xS.device):
         counts = torch.empty(2 * T, dtype=torch.int64, device=xS.device)
         _lib.check(lib.fc_twin_count_dense(_ptr(xSc), xSc.shape[0], _ptr(xTc), xTc.shape[0], xSc.shape[1], _DTYPES[xS.dtype],
                                            (ctypes.c_double * T)(*thr), T, _ptr(counts), _stream()), 'fc_twin_count_dense')
@@ -196,9 +189,9 @@ class _LabelSmoothing(torch.autograd.Function):
         x = pred.detach().contiguous()
         N, K = int(x.shape[0]), int(x.shape[1])
         dev, dt = x.device, x.dtype
-        with torch.cuda.device(dev):
+        with _on(dev):
             nbytes = lib.fc_label_smoothing_workspace_bytes(N, K)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = _scratch(nbytes, dev)
             loss = torch.empty(1, dtype=dt, device=dev)
             _lib.check(lib.fc_label_smoothing_forward(_ptr(x), _ptr(target), _ptr(weight), N, K, _DTYPES[dt], conf, off, _ptr(loss),
                                                       _ptr(ws), nbytes, _stream()), 'fc_label_smoothing_forward')
@@ -211,7 +204,7 @@ class _LabelSmoothing(torch.autograd.Function):
         lib = _lib.load()
         x, target, weight = ctx.saved_tensors
         N, K = int(x.shape[0]), int(x.shape[1])
-        with torch.cuda.device(x.device):
+        with _on(x.device):
             g = g.detach().to(x.dtype).reshape(1).contiguous()
             gpred = torch.empty((N, K), dtype=x.dtype, device=x.device)
             _lib.check(lib.fc_label_smoothing_backward(_ptr(x), _ptr(target), _ptr(weight), _ptr(g), N, K, _DTYPES[x.dtype], ctx.conf,

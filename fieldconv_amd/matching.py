@@ -4,26 +4,15 @@ Features are real (N,C) float32 or float64 tensors on a ROCm device, as in field
 [row of xT, row of xS].  The distance is the losses' d2, bit for bit (one definition in the library), so a match and its
 TwinEval verdict cannot disagree at a threshold, and the N_T x N_S matrix never exists: memory is O(N_T k).  There is no CPU
 or eager path: a CPU tensor raises.  Nothing here is differentiable."""
-import operator
-
 import torch
 
 from . import _lib
-from .losses import _DTYPES, _features, _ptr, _stream
+from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
+from .losses import _DTYPES, _features
 from .pooling import check_ptr, ptr_on
 
 MAX_K = 8
 MAX_PARTS = 1024
-
-
-def _whole(v, lo, hi, what, name):
-    try:
-        n = None if isinstance(v, bool) else operator.index(v)
-    except TypeError:
-        n = None
-    if n is None or not lo <= n <= hi:
-        raise ValueError(f'{what}: {name} must be an integer in [{lo}, {hi}], got {v!r}')
-    return n
 
 
 def match_descriptors(xS, xT, k=1, ptr_S=None, ptr_T=None, exclude=None, parts=0):
@@ -68,9 +57,9 @@ def match_descriptors(xS, xT, k=1, ptr_S=None, ptr_T=None, exclude=None, parts=0
         ptr_T, ptr_S = ptr_on(ptr_T, host_T, dev), ptr_on(ptr_S, host_S, dev)
     lib = _lib.load()
     xSc, xTc = xS.detach().contiguous(), xT.detach().contiguous()
-    with torch.cuda.device(dev):
+    with _on(dev):
         nbytes = lib.fc_match_workspace_bytes(n_T, k, parts)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws = _scratch(nbytes, dev, None)
         idx = torch.empty((n_T, k), dtype=torch.int64, device=dev)
         d2 = torch.empty((n_T, k), dtype=dt, device=dev)
         _lib.check(lib.fc_match_topk(_ptr(xSc), n_S, _ptr(xTc), n_T, C, _DTYPES[dt], _ptr(ptr_S), _ptr(ptr_T), B, _ptr(exclude), k, parts,

@@ -13,28 +13,14 @@ any change of frames:
 
 Features are (N,C) complex tensors on a ROCm device; there is no CPU or eager path: a CPU tensor raises.  The range table ptr is
 handled as fieldconv_amd.pooling handles it: a MeshBatch's ptr costs no synchronisation."""
-import ctypes
-
 import torch
 
 from . import _lib
+from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
 from .pooling import check_ptr, ptr_on, tag_ptr
 
 _DTYPES = {torch.complex64: 0, torch.complex128: 1}
 _REAL = {torch.complex64: torch.float32, torch.complex128: torch.float64}
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _workspace(lib, N, B, C, dt, dev):
-    nbytes = lib.fc_tangent_norm_workspace_bytes(N, B, C, dt)
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
 
 
 class _TangentNorm(torch.autograd.Function):
@@ -46,8 +32,9 @@ class _TangentNorm(torch.autograd.Function):
         dev, dt, real = xc.device, _DTYPES[xc.dtype], _REAL[xc.dtype]
         gc = None if gain is None else gain.detach().reshape(-1).contiguous()
         wc = None if w is None else w.detach().reshape(-1).contiguous()
-        with torch.cuda.device(dev):
-            ws, nbytes = _workspace(lib, N, B, C, dt, dev)
+        with _on(dev):
+            nbytes = lib.fc_tangent_norm_workspace_bytes(N, B, C, dt)
+            ws = _scratch(nbytes, dev, 1)
             y = torch.empty((N, C), dtype=xc.dtype, device=dev)
             r = torch.empty((B, C), dtype=real, device=dev)
             _lib.check(lib.fc_tangent_norm_forward(_ptr(xc), _ptr(wc), _ptr(ptr), _ptr(gc), N, B, C, dt, float(eps), _ptr(y), _ptr(r), _ptr(ws),
@@ -65,9 +52,10 @@ class _TangentNorm(torch.autograd.Function):
         x, gain, ptr, w, r = ctx.saved_tensors
         N, C, B, dt, gain_shape = ctx.meta
         dev = x.device
-        with torch.cuda.device(dev):
+        with _on(dev):
             gy = gy.detach().to(x.dtype).resolve_conj().resolve_neg().contiguous()
-            ws, nbytes = _workspace(lib, N, B, C, dt, dev)
+            nbytes = lib.fc_tangent_norm_workspace_bytes(N, B, C, dt)
+            ws = _scratch(nbytes, dev, 1)
             gx = torch.empty((N, C), dtype=x.dtype, device=dev) if need_x else None
             gg = torch.empty((C,), dtype=r.dtype, device=dev) if need_gain else None
             if N > 0 or need_gain:

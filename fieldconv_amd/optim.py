@@ -5,11 +5,10 @@ gradient buffer), so that an optimizer step is one elementwise HIP kernel (csrc/
 `zero_grad` at most one fill.  The step counter lives on the device: the update is capturable in a HIP graph together with the
 forward and backward passes (fieldconv_amd.utils.StepGraph).  Arithmetic of torch.optim.Adam (L2 weight decay, no amsgrad).
 """
-import ctypes
-
 import torch
 
 from . import _lib
+from ._launch import _p, on as _on, stream as _stream
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -133,10 +132,8 @@ class FusedAdam(torch.optim.Optimizer):
         g = self.param_groups[0]
         self._pack_grads()
         lib = _lib.load()
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        with torch.cuda.device(self._flat.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(lib.fc_adam_step(p(self._flat), p(self._grad), p(self._m), p(self._v), p(self._step), self._n, float(g['lr']),
-                                        float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), st),
+        with _on(self._flat.device):
+            _lib.check(lib.fc_adam_step(_p(self._flat), _p(self._grad), _p(self._m), _p(self._v), _p(self._step), self._n, float(g['lr']),
+                                        float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), _stream()),
                        'fc_adam_step')
         return loss

@@ -6,23 +6,14 @@ ascending, ptr[0] = 0, ptr[-1] = N; MeshBatch.ptr).  Features are (N,C) tensors 
 path: a CPU tensor raises.  ptr may live on the host or on the device.  Its VALUES are checked on the host before anything
 is launched: a host ptr costs nothing, a MeshBatch's ptr carries its host copy along, and any other device ptr is read back
 once -- the one synchronisation -- and remembered for as long as the tensor is not modified."""
-import ctypes
-
 import torch
 
 from . import _lib
+from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
 
 _DTYPES = {torch.float32: 0, torch.float64: 1, torch.complex64: 0, torch.complex128: 1}
 _REAL = {torch.complex64: torch.float32, torch.complex128: torch.float64}
 _REDUCE = {'mean': 0, 'sum': 1}
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def tag_ptr(ptr, host):
@@ -62,6 +53,14 @@ def ptr_on(ptr, host, device):
     return tag_ptr(ptr.to(device).contiguous(), host)
 
 
+def per_mesh(value, B, what, name):
+    """An argument given once for all B meshes, or as a list, tuple or tensor with one entry per mesh -> the list of B entries."""
+    vals = list(value) if isinstance(value, (list, tuple)) or torch.is_tensor(value) else [value] * B
+    if len(vals) != B:
+        raise ValueError(f'{what}: {name} must be one integer or one per mesh ({B}), got {len(vals)}')
+    return vals
+
+
 class _MeshPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ptr, reduce, soft_abs):
@@ -70,9 +69,9 @@ class _MeshPool(torch.autograd.Function):
         N, C, B = int(xc.shape[0]), int(xc.shape[1]), int(ptr.numel()) - 1
         dev, dt = xc.device, _DTYPES[xc.dtype]
         rdt = _REAL[xc.dtype] if soft_abs else xc.dtype
-        with torch.cuda.device(dev):
+        with _on(dev):
             nbytes = lib.fc_segment_pool_workspace_bytes(N, B, C, dt)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            ws = _scratch(nbytes, dev, 1)
             out = torch.empty((B, C), dtype=rdt, device=dev)
             fn, name = (lib.fc_segment_pool_soft_abs_forward, 'fc_segment_pool_soft_abs_forward') if soft_abs else \
                        (lib.fc_segment_pool_forward, 'fc_segment_pool_forward')
@@ -87,7 +86,7 @@ class _MeshPool(torch.autograd.Function):
         x, ptr = ctx.saved_tensors
         N, C, B, dt, reduce, soft_abs, xdt = ctx.meta
         dev = ptr.device
-        with torch.cuda.device(dev):
+        with _on(dev):
             g = g.detach().to(_REAL[xdt] if soft_abs else xdt).contiguous()
             gx = torch.empty((N, C), dtype=xdt, device=dev)
             if soft_abs:

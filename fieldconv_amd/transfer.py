@@ -17,8 +17,8 @@ weight and phase are geometry: they never receive a gradient."""
 import torch
 
 from . import _lib
-from .geodesic import (_batch_tables, _check_diagonals, _check_index, _check_mesh, _device_of, _ptr, _segment_sum, _stream, mesh_edge_graph,
-                       nearest_sample)
+from ._launch import device_of as _device_of, on as _on, ptr as _ptr, stream as _stream, whole as _whole
+from .geodesic import _batch_tables, _check_diagonals, _check_index, _check_mesh, _segment_sum, mesh_edge_graph, nearest_sample
 from .logmap import _check_bound, log_map_transport
 
 _DTYPES = {torch.float32: (0, 0), torch.float64: (1, 0), torch.complex64: (0, 1), torch.complex128: (1, 1)}          # (fc_dtype, is_complex)
@@ -39,16 +39,6 @@ class _Csr(object):
             self._cast[real] = (self.weight.to(real).contiguous(),
                                 None if self.phase is None else self.phase.to(_COMPLEX[real]).contiguous())
         return self._cast[real]
-
-
-def _whole(v, what, name):
-    try:
-        ok = not isinstance(v, bool) and int(v) == v and 0 <= v < 2 ** 31 - 1
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f'{what}: {name} must be an integer in [0, 2^31 - 1), got {v!r}')
-    return int(v)
 
 
 class TransferPlan(object):
@@ -84,7 +74,8 @@ class TransferPlan(object):
                 raise ValueError(f'{what}: phase must have one entry per row, ({E},), got {tuple(phase.shape)}')
         if n_out is None or n_in is None:
             raise ValueError(f'{what}: n_out and n_in, the numbers of output and input rows, must be given')
-        n_out, n_in = _whole(n_out, what, 'n_out'), _whole(n_in, what, 'n_in')
+        n_out = _whole(n_out, 0, 2 ** 31 - 2, what, 'n_out', integral_floats=True)
+        n_in = _whole(n_in, 0, 2 ** 31 - 2, what, 'n_in', integral_floats=True)
         if E >= 2 ** 31 - 1:
             raise ValueError(f'{what}: slots are 32-bit indices in the kernel: at most 2^31 - 2 rows, got {E}')
         if not isinstance(conj_phase, bool):
@@ -95,8 +86,8 @@ class TransferPlan(object):
                 raise ValueError(f'{what}: rows[:, 0] must lie in [0, {n_out}), got values from {lo[0]} to {hi[0]}')
             if lo[1] < 0 or hi[1] >= n_in:
                 raise ValueError(f'{what}: rows[:, 1] must lie in [0, {n_in}), got values from {lo[1]} to {hi[1]}')
-        dev = _device_of(rows)
-        with torch.cuda.device(dev):
+        dev = _device_of(rows, 'geodesics')
+        with _on(dev):
             r = rows.detach().to(dev)
             w = weight.detach().to(dev)
             ph = None if phase is None else phase.detach().to(dev).resolve_conj()
@@ -139,7 +130,7 @@ def _launch(x, plan):
     C = int(x.shape[1])
     csr = plan._fwd
     w, ph = csr.coefficients(_REAL[dt])
-    with torch.cuda.device(x.device):
+    with _on(x.device):
         y = torch.empty((plan.n_out, C), dtype=x.dtype, device=x.device)
         _lib.check(lib.fc_transfer(_ptr(x), _ptr(csr.rowptr), _ptr(csr.col), _ptr(w), _ptr(ph) if cplx else None, int(plan.conj_phase and cplx),
                                    plan.n_out, plan.n_in, plan.n_rows, C, dt, cplx, _ptr(y), _stream()), 'fc_transfer')
@@ -264,11 +255,11 @@ def level_transfer(pos, face, sample_idx, coarse, w_fine, graph=None, diagonals=
                          f'{(tuple(w_fine.shape), w_fine.dtype) if torch.is_tensor(w_fine) else type(w_fine).__name__}')
     if bound is not None:
         bound = _check_bound(bound, what)
-    dev = _device_of(pos)
+    dev = _device_of(pos, 'geodesics')
     if graph is None:
         graph = mesh_edge_graph(pos, face, diagonals)
     cell, dist = sample_cells(pos, face, sample_idx, coarse, graph=graph, pos_ptr=pos_ptr, ptr=ptr, coarse_ptr=coarse_ptr)
-    with torch.cuda.device(dev):
+    with _on(dev):
         cell, dist = cell.to(dev), dist.to(dev)
         member = torch.nonzero(cell >= 0)[:, 0]          # ascending f
         c = cell[member]
@@ -296,15 +287,10 @@ KNN_MAX = 16          # fc_knn_weights keeps a row's best k in registers: 1 <= k
 
 
 def _check_knn(k, power, what):
-    try:
-        ok = not isinstance(k, bool) and int(k) == k and 1 <= k <= KNN_MAX
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f'{what}: k must be an integer in [1, {KNN_MAX}], got {k!r}')
+    k = _whole(k, 1, KNN_MAX, what, 'k', integral_floats=True)
     if isinstance(power, bool) or power not in (1, 2):
         raise ValueError(f'{what}: power must be 1 or 2, got {power!r}')
-    return int(k), int(power)
+    return k, int(power)
 
 
 def knn_weights(rowptr, cand, dist, k=3, power=2):
@@ -329,7 +315,7 @@ def knn_weights(rowptr, cand, dist, k=3, power=2):
         raise ValueError(f'{what}: n_f * k must stay below 2^31, got {n_f} x {k}')
     lib = _lib.load()
     rowptr, cand, dist = rowptr.contiguous(), cand.contiguous(), dist.contiguous()
-    with torch.cuda.device(rowptr.device):
+    with _on(rowptr.device):
         sel = torch.empty((n_f, k), dtype=torch.int32, device=rowptr.device)
         weight = torch.empty((n_f, k), dtype=torch.float32, device=rowptr.device)
         _lib.check(lib.fc_knn_weights(_ptr(rowptr), _ptr(cand) if n_slots else None, _ptr(dist) if n_slots else None, n_f, n_slots, k, power,
@@ -376,7 +362,7 @@ def interpolation_plan(pos, face, sample_idx, coarse, k=3, power=2, radius=None,
     if not isinstance(return_rows, bool):
         raise ValueError(f'{what}: return_rows must be True or False, got {return_rows!r}')
     from .geodesic_sampling import geodesic_radius_edges
-    dev = _device_of(pos)
+    dev = _device_of(pos, 'geodesics')
     if graph is None:
         graph = mesh_edge_graph(pos, face, diagonals)
     trivial = False
@@ -391,7 +377,7 @@ def interpolation_plan(pos, face, sample_idx, coarse, k=3, power=2, radius=None,
             radius = _check_bound(float(up), what)
         else:
             trivial = True
-    with torch.cuda.device(dev):
+    with _on(dev):
         if trivial:          # no tree to grow: every member sits on its coarse sample
             f = torch.nonzero(inside)[:, 0]
             c = cell[f]

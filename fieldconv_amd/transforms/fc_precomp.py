@@ -3,10 +3,11 @@ every operator of this package.  By default the call goes from the inputs STRAIG
 records the convolutions consume (fc_precomp_mark + fc_precomp_graph, csrc/fc_graph.hip) and returns a FactoredStencil in
 place of the (E,R,F) tensor -- the dense stencil (154 MB at BASELINE configs[1]) is built only if something asks for it.
 FIELDCONV_EAGER_STENCIL=1 keeps the reference's literal outputs (fc_precomp_build)."""
-import ctypes
 import os
 
 import torch
+
+from .._launch import _po, on as _on, scratch as _scratch, stream as _stream
 
 
 class FCPrecomp(object):
@@ -64,13 +65,12 @@ class FCPrecomp(object):
         wv = w.reshape(-1).contiguous()
         edges = supp_edges.to(torch.int64).contiguous()
         eps = float(self.max_r)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(dev):
-            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        with _on(dev):
+            st = _stream()
             nbytes = lib.fc_precomp_workspace_bytes(N, E)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.fc_precomp_mark(p(r), p(edges), eps, N, E, p(ws), nbytes, st), 'fc_precomp_mark')
-            off = lib.fc_precomp_kept_count_ptr(p(ws), E) - ws.data_ptr()
+            ws = _scratch(nbytes, dev)
+            _lib.check(lib.fc_precomp_mark(_po(r), _po(edges), eps, N, E, _po(ws), nbytes, st), 'fc_precomp_mark')
+            off = lib.fc_precomp_kept_count_ptr(_po(ws), E) - ws.data_ptr()
             kept, bad = ws[off:off + 8].view(torch.int32).tolist()        # the one synchronisation (the reference's `nonzero`);
             if bad:                                                       # early, while little is queued: the host enqueues
                 raise IndexError(f'supp_edges refers to a vertex outside [0, {N})')      # the rest without waiting again
@@ -82,8 +82,8 @@ class FCPrecomp(object):
             literal = R > 8 or F > 7 or not lib.fc_shape_compiled(R, self.B)     # no record-driven kernels for this shape: the literal (E',R,F) rows
             if literal or os.environ.get('FIELDCONV_EAGER_STENCIL', '0') == '1' or os.environ.get('FIELDCONV_DENSE', '0') == '1':
                 sten = torch.empty((kept, R, F), **c64)
-                _lib.check(lib.fc_precomp_build(p(r), p(theta), p(xp), p(wv), p(edges), eps, N, E, R, F, p(edges_out), p(sten), p(ln),
-                                                p(wxp), p(ws), nbytes, st), 'fc_precomp_build')
+                _lib.check(lib.fc_precomp_build(_po(r), _po(theta), _po(xp), _po(wv), _po(edges), eps, N, E, R, F, _po(edges_out), _po(sten), _po(ln),
+                                                _po(wxp), _po(ws), nbytes, st), 'fc_precomp_build')
                 return edges_out.to(supp_edges.dtype), sten, ln, wxp
             # fused: records and both groupings straight from the inputs
             from ..graph import FactoredStencil, SupportGraph, register_graph
@@ -116,11 +116,11 @@ class FCPrecomp(object):
             if not want_geo:
                 b['geo_t'] = None
             factors = b['factors']
-            gws = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.fc_precomp_graph(p(r), p(theta), p(xp), p(wv), p(edges), eps, N, E, kept, R, F, pad_rec, pad_geo,
-                                            p(edges_out), p(ln), p(wxp), p(factors), p(b['rowptr_t']), p(b['nbr_t']), p(b['runs_t']),
-                                            p(b['perm_t']), p(b['rowptr_s']), p(b['nbr_s']), p(b['runs_s']), p(b['perm_s']),
-                                            p(b['rec_t']), p(b['rec_s']), p(b['geo_t']), p(b['flags']), p(ws), nbytes, p(gws), gbytes, st),
+            gws = _scratch(gbytes, dev)
+            _lib.check(lib.fc_precomp_graph(_po(r), _po(theta), _po(xp), _po(wv), _po(edges), eps, N, E, kept, R, F, pad_rec, pad_geo,
+                                            _po(edges_out), _po(ln), _po(wxp), _po(factors), _po(b['rowptr_t']), _po(b['nbr_t']), _po(b['runs_t']),
+                                            _po(b['perm_t']), _po(b['rowptr_s']), _po(b['nbr_s']), _po(b['runs_s']), _po(b['perm_s']),
+                                            _po(b['rec_t']), _po(b['rec_s']), _po(b['geo_t']), _po(b['flags']), _po(ws), nbytes, _po(gws), gbytes, st),
                        'fc_precomp_graph')
         edges_ret = edges_out.to(supp_edges.dtype)
         graph = SupportGraph.from_precomp(edges_ret, N, R, F, b, want_geo)

@@ -2,10 +2,12 @@
 then every sample's neighbours within epsilon.  The arithmetic runs on the ROCm device (csrc/fc_support.hip) whatever
 device the input is on; results go back to the input's device, so the transform also serves as a CPU-side
 `pre_transform`.  There is no CPU arithmetic path."""
-import ctypes
 import math
 
 import torch
+
+from .._launch import device_of as _device_of, on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
+from ..pooling import check_ptr, per_mesh, ptr_on
 
 
 def _check_pos(pos, what):
@@ -30,24 +32,13 @@ def _check_epsilon(epsilon, what):
 
 
 def _check_k(max_num_neighbors, what):
-    if isinstance(max_num_neighbors, bool) or int(max_num_neighbors) != max_num_neighbors or max_num_neighbors < 1:
-        raise ValueError(f'{what}: max_num_neighbors must be an integer >= 1, got {max_num_neighbors!r}')
-    return int(max_num_neighbors)
+    return _whole(max_num_neighbors, 1, 2 ** 63 - 1, what, 'max_num_neighbors', integral_floats=True)
 
 
 def _on_device(pos):
     """pos as contiguous float32 on the ROCm device it is on (CPU input: the current device)."""
-    if pos.is_cuda:
-        dev = pos.device
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError('fieldconv_amd support graphs are computed on a ROCm device and none is visible; there is no CPU path')
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _device_of(pos, 'support graphs')
     return pos.detach().to(device=dev, dtype=torch.float32).contiguous(), dev
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def farthest_point_sample(pos, n_samples, start=0):
@@ -56,20 +47,17 @@ def farthest_point_sample(pos, n_samples, start=0):
     positions repeat.  pos: (N,3); 1 <= n_samples <= N; 0 <= start < N."""
     _check_pos(pos, 'farthest_point_sample')
     N = int(pos.shape[0])
-    if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 1 <= n_samples <= N:
-        raise ValueError(f'farthest_point_sample: n_samples must be an integer in [1, {N}], got {n_samples!r}')
-    if isinstance(start, bool) or int(start) != start or not 0 <= start < N:
-        raise ValueError(f'farthest_point_sample: start must be an integer in [0, {N}), got {start!r}')
+    S = _whole(n_samples, 1, N, 'farthest_point_sample', 'n_samples', integral_floats=True)
+    start = _whole(start, 0, N - 1, 'farthest_point_sample', 'start', integral_floats=True)
     from .. import _lib
     lib = _lib.load()
     p, dev = _on_device(pos)
-    S = int(n_samples)
-    with torch.cuda.device(dev):
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with _on(dev):
+        st = _stream()
         nbytes = lib.fc_fps_workspace_bytes(N)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _scratch(nbytes, dev)
         idx = torch.empty(S, dtype=torch.int64, device=dev)
-        _lib.check(lib.fc_fps(_ptr(p), N, S, int(start), _ptr(idx), _ptr(ws), nbytes, st), 'fc_fps')
+        _lib.check(lib.fc_fps(_ptr(p), N, S, start, _ptr(idx), _ptr(ws), nbytes, st), 'fc_fps')
     return idx.to(pos.device)
 
 
@@ -84,28 +72,16 @@ def radius_edges(pos, epsilon, max_num_neighbors=512):
     lib = _lib.load()
     p, dev = _on_device(pos)
     N = int(pos.shape[0])
-    with torch.cuda.device(dev):
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with _on(dev):
+        st = _stream()
         nbytes = lib.fc_radius_workspace_bytes(N)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _scratch(nbytes, dev)
         _lib.check(lib.fc_radius_count(_ptr(p), N, eps, K, _ptr(ws), nbytes, st), 'fc_radius_count')
         off = lib.fc_radius_edge_count_ptr(_ptr(ws), N) - ws.data_ptr()
         E = int(ws[off:off + 8].view(torch.int64).item())          # the one synchronisation: E sizes the output
         edges = torch.empty((E, 2), dtype=torch.int64, device=dev)
         _lib.check(lib.fc_radius_fill(_ptr(p), N, eps, K, E, _ptr(edges), _ptr(ws), nbytes, st), 'fc_radius_fill')
     return edges.to(pos.device)
-
-
-def _per_mesh(value, B, what, name):
-    vals = [value] * B if not isinstance(value, (list, tuple)) and not torch.is_tensor(value) else list(value)
-    if len(vals) != B:
-        raise ValueError(f'{what}: {name} must be one integer or one per mesh ({B}), got {len(vals)}')
-    out = []
-    for v in vals:
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f'{what}: {name} must hold integers, got {v!r}')
-        out.append(int(v))
-    return out
 
 
 def farthest_point_sample_batched(pos, pos_ptr, n_samples, start=0):
@@ -116,29 +92,26 @@ def farthest_point_sample_batched(pos, pos_ptr, n_samples, start=0):
     farthest_point_sample gives for the set alone."""
     what = 'farthest_point_sample_batched'
     _check_pos(pos, what)
-    from ..pooling import check_ptr, ptr_on
     N = int(pos.shape[0])
     host = check_ptr(pos_ptr, N, what, 'pos_ptr')
     B = len(host) - 1
-    S, st = _per_mesh(n_samples, B, what, 'n_samples'), _per_mesh(start, B, what, 'start')
+    S, st = per_mesh(n_samples, B, what, 'n_samples'), per_mesh(start, B, what, 'start')
     for b in range(B):
         n_b = host[b + 1] - host[b]
-        if not 1 <= S[b] <= n_b:
-            raise ValueError(f'{what}: n_samples of mesh {b} must lie in [1, {n_b}], got {S[b]}')
-        if not 0 <= st[b] < n_b:
-            raise ValueError(f'{what}: start of mesh {b} must lie in [0, {n_b}), got {st[b]}')
+        S[b] = _whole(S[b], 1, n_b, what, 'n_samples', f' of mesh {b}', integral_floats=True)
+        st[b] = _whole(st[b], 0, n_b - 1, what, 'start', f' of mesh {b}', integral_floats=True)
     from .. import _lib
     lib = _lib.load()
     p, dev = _on_device(pos)
     out_ptr = [0]
     for v in S:
         out_ptr.append(out_ptr[-1] + v)
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with _on(dev):
+        stream = _stream()
         tables = torch.tensor([S, st, out_ptr[:-1]], dtype=torch.int64).to(dev)
         ptr_d = ptr_on(pos_ptr, host, dev)
         nbytes = lib.fc_fps_batched_workspace_bytes(N)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _scratch(nbytes, dev)
         idx = torch.empty(out_ptr[-1], dtype=torch.int64, device=dev)
         _lib.check(lib.fc_fps_batched(_ptr(p), _ptr(ptr_d), N, B, _ptr(tables[0]), _ptr(tables[1]), _ptr(tables[2]), out_ptr[-1], _ptr(idx),
                                       _ptr(ws), nbytes, stream), 'fc_fps_batched')
@@ -154,7 +127,6 @@ def radius_edges_batched(pos, ptr, epsilon, max_num_neighbors=512):
     _check_pos(pos, what)
     eps = _check_epsilon(epsilon, what)
     K = _check_k(max_num_neighbors, what)
-    from ..pooling import check_ptr, ptr_on
     N = int(pos.shape[0])
     host = check_ptr(ptr, N, what)
     B = len(host) - 1
@@ -163,11 +135,11 @@ def radius_edges_batched(pos, ptr, epsilon, max_num_neighbors=512):
     from .. import _lib
     lib = _lib.load()
     p, dev = _on_device(pos)
-    with torch.cuda.device(dev):
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with _on(dev):
+        st = _stream()
         ptr_d = ptr_on(ptr, host, dev)
         nbytes = lib.fc_radius_workspace_bytes(N)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _scratch(nbytes, dev)
         _lib.check(lib.fc_radius_count_batched(_ptr(p), _ptr(ptr_d), N, B, eps, K, _ptr(ws), nbytes, st), 'fc_radius_count_batched')
         off = lib.fc_radius_edge_count_ptr(_ptr(ws), N) - ws.data_ptr()
         E = int(ws[off:off + 8].view(torch.int64).item())          # the one synchronisation: E sizes the output
@@ -202,7 +174,6 @@ class SupportGraph(object):
         self.generator = generator
 
     def _call_batch(self, data):
-        from ..pooling import check_ptr
         pos = data.pos
         _check_pos(pos, 'SupportGraph')
         pp = check_ptr(data.pos_ptr, int(pos.shape[0]), 'SupportGraph', 'pos_ptr')

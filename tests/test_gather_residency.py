@@ -23,12 +23,13 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture()
 def guarded(monkeypatch):
+    import fieldconv_amd._launch as launch
     import fieldconv_amd.blocks as blocks
     import fieldconv_amd.functional as Fn
     import fieldconv_amd.graph as graph
     import fieldconv_amd.transforms.fc_precomp as pre
     g = GuardedTorch()
-    for mod in (Fn, blocks, graph, pre):
+    for mod in (launch, Fn, blocks, graph, pre):
         monkeypatch.setattr(mod, 'torch', g)
     monkeypatch.setenv('FIELDCONV_CPP_NODES', '0')      # (the C++ nodes allocate inside torch's C++ API, where the stand-in does not reach)
     return g

@@ -69,6 +69,7 @@ class GuardedTorch:
 
 @pytest.fixture()
 def guarded(monkeypatch):
+    import fieldconv_amd._launch as launch
     import fieldconv_amd.blocks as blocks
     import fieldconv_amd.functional as Fn
     import fieldconv_amd.graph as graph
@@ -80,7 +81,7 @@ def guarded(monkeypatch):
     import fieldconv_amd.transforms.fc_precomp as pre
     import fieldconv_amd.transforms.support_graph as support
     g = GuardedTorch()
-    for mod in (Fn, blocks, graph, pre, norm, pooling, losses, head, matching, support):
+    for mod in (launch, Fn, blocks, graph, pre, norm, pooling, losses, head, matching, support):
         monkeypatch.setattr(mod, 'torch', g)
     # the host-side nodes in Python: the C++ nodes allocate inside torch's C++ API, where this stand-in does not reach
     monkeypatch.setenv('FIELDCONV_CPP_NODES', '0')

@@ -313,10 +313,12 @@ def test_mesh_batch_per_mesh_means(dev):
 def test_no_write_outside_any_buffer(dev, monkeypatch):
     """Guard bands as in tests/test_gpu_canary.py: every buffer the head allocates (outputs, lse, workspaces, gradients) is carved
     out of a larger allocation whose margins hold a byte pattern; ragged N, H, K, parts 0 / 1 / 3."""
+    import fieldconv_amd._launch as launch
     import fieldconv_amd.head as head
     from test_gpu_canary import GuardedTorch
     g = GuardedTorch()
     monkeypatch.setattr(head, 'torch', g)
+    monkeypatch.setattr(launch, 'torch', g)
     N, H, K = 131, 37, 203
     h, W, b, target, _ = inputs(N, H, K)
     n = 0

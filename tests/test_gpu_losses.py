@@ -348,9 +348,10 @@ class _GuardedTorch:
 def test_no_write_outside_any_buffer(dev, monkeypatch, n_T, n_S, C, P, M):
     """Every output, saved buffer and workspace of the loss entry points is carved out of a larger allocation whose margins hold a
     byte pattern; after forward + backward of each family the margins are untouched."""
-    from fieldconv_amd import losses
+    from fieldconv_amd import _launch, losses
     g = _GuardedTorch()
     monkeypatch.setattr(losses, 'torch', g)
+    monkeypatch.setattr(_launch, 'torch', g)
     rng = np.random.default_rng(P)
     xS_np, xT_np = _features(n_T, n_S, C, seed=7)
     pos = T(np.stack((rng.integers(0, n_T, P), rng.integers(0, n_S, P)), 1), dev)

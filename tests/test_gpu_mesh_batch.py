@@ -348,9 +348,11 @@ def test_mesh_pool_gradcheck_float64(dev):
 def test_mesh_pool_writes_inside_its_buffers(dev, monkeypatch):
     """Output, workspace and gradient carved out of guarded allocations, as tests/test_gpu_canary.py does for the other entry points."""
     from test_gpu_canary import GuardedTorch
+    import fieldconv_amd._launch as launch
     import fieldconv_amd.pooling as pooling
     guarded = GuardedTorch()
     monkeypatch.setattr(pooling, 'torch', guarded)
+    monkeypatch.setattr(launch, 'torch', guarded)
     n = 0
     for C in (1, 48, 130):
         for soft_abs, dtype in ((True, 'f32'), (False, 'f32'), (True, 'f64'), (False, 'f64')):

@@ -262,11 +262,13 @@ def test_module_in_double_precision(dev):
 def test_no_write_outside_any_buffer(dev, monkeypatch, dtype):
     """x, gy, w, gain, ptr, y, r, gx, ggain and both workspaces sit between guard bands (tests/test_gpu_canary.py); C = 65"""
     from test_gpu_canary import GuardedTorch
+    import fieldconv_amd._launch as launch
     import fieldconv_amd.norm as norm
     from fieldconv_amd.pooling import tag_ptr
     tdt, rdt, real = DTYPES[dtype]
     g = GuardedTorch()
     monkeypatch.setattr(norm, 'torch', g)
+    monkeypatch.setattr(launch, 'torch', g)
 
     def guarded_copy(t):
         out = g._guarded(tuple(t.shape), t.dtype, t.device)

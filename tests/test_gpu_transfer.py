@@ -328,9 +328,11 @@ def test_encoder_decoder_on_the_sphere_pair(dev):
 def test_no_write_outside_any_buffer(dev, monkeypatch):
     """x, y, gx and every plan buffer sit between guard bands (tests/test_gpu_canary.py); C = 70 and the 200-slot row"""
     from test_gpu_canary import GuardedTorch
+    import fieldconv_amd._launch as launch
     import fieldconv_amd.transfer as transfer
     g = GuardedTorch()
     monkeypatch.setattr(transfer, 'torch', g)
+    monkeypatch.setattr(launch, 'torch', g)
 
     def guarded_copy(t):
         if t is None:
