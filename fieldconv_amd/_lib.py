@@ -236,6 +236,10 @@ SIGNATURES = {
     'fc_tangent_norm_forward': (ctypes.c_int, [_vp] * 4 + [_c_int32] * 4 + [ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
     'fc_tangent_norm_backward': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 4 + [_vp, _vp, _vp, _sz, _vp]),
     'fc_knn_weights': (ctypes.c_int, [_vp] * 3 + [_c_int32] * 4 + [_vp] * 3),
+    'fc_transfer_max': (ctypes.c_int, [_vp] * 4 + [_c_int32] * 7 + [_vp] * 3),
+    'fc_transfer_max_backward': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 7 + [_vp, _vp]),
+    'fc_segment_max_forward': (ctypes.c_int, [_vp, _vp] + [_c_int32] * 5 + [_vp] * 5),
+    'fc_segment_max_backward': (ctypes.c_int, [_vp] * 4 + [_c_int32] * 5 + [_vp, _vp]),
 }
 
 _LIB = None

@@ -876,7 +876,7 @@ def soft_abs(x):
     return softAbs(x)
 
 
-from .pooling import mesh_mean, mesh_pool          # noqa: E402,F401  (per-mesh pooling over a MeshBatch: csrc/fc_segment.hip)
+from .pooling import mesh_max, mesh_mean, mesh_pool          # noqa: E402,F401  (per-mesh pooling over a MeshBatch: csrc/fc_segment.hip, fc_maxpool.hip)
 from .matching import match_accuracy, match_descriptors, mutual_matches          # noqa: E402,F401  (nearest rows: csrc/fc_match.hip)
 from .head import linear_cross_entropy, linear_logsumexp, linear_topk, vertex_accuracy          # noqa: E402,F401  (the fused classification head: csrc/fc_linear_ce.hip)
 
@@ -1137,6 +1137,6 @@ from .geodesic import (compose_map, correspondence_curve, geodesic_distances, ge
 from .geodesic_sampling import (geodesic_farthest_point_sample, geodesic_farthest_point_sample_batched,          # noqa: E402,F401  (csrc/fc_geodesic_fps.hip)
                                 geodesic_radius_edges)
 from .logmap import log_map_transport, vertex_frames          # noqa: E402,F401  (csrc/fc_logmap.hip)
-from .transfer import TransferPlan, level_transfer, sample_cells, tangent_transfer          # noqa: E402,F401  (csrc/fc_transfer.hip)
+from .transfer import TransferPlan, level_transfer, sample_cells, tangent_transfer, tangent_transfer_max          # noqa: E402,F401  (csrc/fc_transfer.hip, fc_maxpool.hip)
 from .transfer import interpolation_plan, knn_weights, vertex_interpolation          # noqa: E402,F401  (csrc/fc_interp.hip)
 from .norm import tangent_norm          # noqa: E402,F401  (csrc/fc_norm.hip)

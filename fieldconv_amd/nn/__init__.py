@@ -16,7 +16,10 @@ from ..head import vertex_accuracy
 from .tangent_pool import TangentPool, TangentUnpool
 from .tangent_norm import TangentNorm
 from .tangent_interpolate import TangentInterpolate
+from .tangent_max_pool import TangentMaxPool
+from .mesh_max_pool import MeshMaxPool
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
            'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval',
-           'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'TangentNorm', 'TangentInterpolate', 'MeshPool']
+           'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'TangentNorm', 'TangentInterpolate',
+           'TangentMaxPool', 'MeshMaxPool', 'MeshPool']

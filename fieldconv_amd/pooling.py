@@ -1,5 +1,6 @@
 """Per-mesh pooling over a mini-batch of meshes (csrc/fc_segment.hip): the functional forms and the autograd function under
-fieldconv_amd.nn.MeshPool and fieldconv_amd.functional.mesh_mean.
+fieldconv_amd.nn.MeshPool and fieldconv_amd.functional.mesh_mean; and mesh_max, the max read-out by magnitude under
+fieldconv_amd.nn.MeshMaxPool (csrc/fc_maxpool.hip).
 
 A mini-batch is a disjoint union: mesh b owns the rows ptr[b] .. ptr[b+1] - 1 of every per-vertex tensor (ptr: (B+1,) int64,
 ascending, ptr[0] = 0, ptr[-1] = N; MeshBatch.ptr).  Features are (N,C) tensors on a ROCm device; there is no CPU or eager
@@ -119,6 +120,74 @@ def mesh_pool(x, ptr, reduce='mean', soft_abs=True, what='mesh_pool'):
     if N + 64 * (len(host) - 1) >= 2 ** 31 - 1:
         raise ValueError(f'{what}: rows + 64 * meshes must stay below 2^31')
     return _MeshPool.apply(x, ptr_on(ptr, host, x.device), _REDUCE[reduce], bool(soft_abs))
+
+
+class _MeshMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ptr):
+        lib = _lib.load()
+        xc = x.detach().resolve_conj().resolve_neg().contiguous()
+        N, C, B = int(xc.shape[0]), int(xc.shape[1]), int(ptr.numel()) - 1
+        dev, dt, cplx = xc.device, _DTYPES[xc.dtype], int(xc.is_complex())
+        rdt = _REAL[xc.dtype] if cplx else xc.dtype
+        with _on(dev):
+            slots = N // 64 + B          # the chunk slots of csrc/fc_segment.hpp: room for every mesh's chunks, whatever ptr holds
+            pkey = torch.empty((slots, C), dtype=rdt, device=dev)
+            prow = torch.empty((slots, C), dtype=torch.int32, device=dev)
+            out = torch.empty((B, C), dtype=rdt, device=dev)
+            index = torch.empty((B, C), dtype=torch.int32, device=dev)
+            _lib.check(lib.fc_segment_max_forward(_ptr(xc), _ptr(ptr), N, B, C, dt, cplx, _ptr(out), _ptr(index), _ptr(pkey), _ptr(prow),
+                                                  _stream()), 'fc_segment_max_forward')
+        ctx.save_for_backward(xc if cplx else None, ptr, index)
+        ctx.meta = (N, C, B, dt, cplx, xc.dtype)
+        ctx.mark_non_differentiable(index)
+        return out, index
+
+    @staticmethod
+    def backward(ctx, g, _):
+        lib = _lib.load()
+        x, ptr, index = ctx.saved_tensors
+        N, C, B, dt, cplx, xdt = ctx.meta
+        dev = ptr.device
+        with _on(dev):
+            g = g.detach().to(_REAL[xdt] if cplx else xdt).contiguous()
+            gx = torch.empty((N, C), dtype=xdt, device=dev)
+            _lib.check(lib.fc_segment_max_backward(_ptr(x), _ptr(g), _ptr(index), _ptr(ptr), N, B, C, dt, cplx, _ptr(gx), _stream()),
+                       'fc_segment_max_backward')
+        return gx, None
+
+
+def mesh_max(x, ptr, soft_abs=True, return_indices=False, what='mesh_max'):
+    """(B,C) real tensor: per mesh and channel the ONE row of largest key (csrc/fc_maxpool.hip, include/fieldconv_hip.h).
+      key      complex64 / complex128 x (N,C), soft_abs=True (the only mode for complex input): k = fl(fl(re * re) + fl(im * im)) in
+               x's scalar type, every operation rounded on its own -- the squared magnitude, which does not depend on the row's
+               frame.  float32 / float64 x, soft_abs=False: k = x itself, a plain max.
+      winner   the row n* of mesh b (rows ptr[b] .. ptr[b+1] - 1) with the largest key; ties go to the smallest row.  NaN is outside
+               the contract.
+      value    complex: out[b,c] = softAbs(x[n*,c]): |x| outside the origin box, 0 inside (reference utils/field.py:29-37); |x| is
+               never written per row.  It is the softAbs of the entry of largest key: softAbs is not strictly monotone in |x| at the
+               corner of the origin box, so another row may have a larger softAbs.  Real: x[n*,c], bit for bit.
+    An empty mesh gives 0, index -1 and no gradient.  With return_indices also the (B,C) int64 winning rows.  Two launches
+    forward (partial winners per chunk of 64 rows, then one combination per mesh, both in the (key, row) order: the result is a
+    plain argmax whatever the chunking), one backward, no atomics: the same bits on every run and for a mesh alone or inside a
+    batch.  Gradient flows to x: g[b,c] * x / |x| outside the origin box (0 inside) at the winner, g[b,c] for real x, and exactly 0
+    at every other row.  Checks are mesh_pool's; a MeshBatch's ptr costs no synchronisation."""
+    if not isinstance(soft_abs, bool) or not isinstance(return_indices, bool):
+        raise ValueError(f'{what}: soft_abs and return_indices must be True or False, got {soft_abs!r} and {return_indices!r}')
+    want = (torch.complex64, torch.complex128) if soft_abs else (torch.float32, torch.float64)
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype not in want:
+        raise ValueError(f'{what}: x must be an (N,C) ' + ('complex64 or complex128' if soft_abs else 'float32 or float64') +
+                         f' tensor, got {(tuple(x.shape), x.dtype) if torch.is_tensor(x) else type(x).__name__}')
+    if not x.is_cuda:
+        raise RuntimeError(f'{what}: x is on {x.device}; fieldconv_amd pooling runs on a ROCm device and has no CPU path')
+    N, C = int(x.shape[0]), int(x.shape[1])
+    if C < 1 or C > 64 * 65535:
+        raise ValueError(f'{what}: between 1 and {64 * 65535} channels, got {C}')
+    host = check_ptr(ptr, N, what)
+    if N + 64 * (len(host) - 1) >= 2 ** 31 - 1:
+        raise ValueError(f'{what}: rows + 64 * meshes must stay below 2^31')
+    out, index = _MeshMax.apply(x, ptr_on(ptr, host, x.device))
+    return (out, index.to(torch.int64)) if return_indices else out
 
 
 def mesh_mean(values, ptr):

@@ -6,6 +6,8 @@ with a deterministic gradient, the plan that holds its two CSRs, and the glue th
 package's own geodesics: nearest-sample cells (geodesic.nearest_sample), sample masses (data.w) and the transport phase along a
 shortest-path tree (logmap.log_map_transport).  interpolation_plan / vertex_interpolation build the smooth counterpart of the
 unpool plan: every receiver from its k nearest coarse samples with inverse-distance weights (csrc/fc_interp.hip).
+tangent_transfer_max is max pooling over the rows of a plan (csrc/fc_maxpool.hip): per output row and channel the ONE member of
+largest magnitude, transported into the receiver's frame.
 
 A tangent-vector feature lives in its sample's frame, so a plain mean over a cell is wrong: every term is parallel-transported
 into the receiving sample's frame first, which is a multiplication by a unit complex number -- the phase of a row.  Real
@@ -28,10 +30,11 @@ _COMPLEX = {torch.float32: torch.complex64, torch.float64: torch.complex128}
 
 class _Csr(object):
     """One CSR by output row on the device: rowptr (n_rows+1,) int32, col (E,) int32, weight (E,) and phase (E,) or None in slot
-    order; the casts of weight and phase to a feature's scalar type are made once and kept."""
+    order; the casts of weight and phase to a feature's scalar type are made once and kept.  other (E,) int32: the slot number of
+    every slot in the plan's other CSR (its transpose) -- what the gradient of a max needs to recognise a winning slot."""
 
-    def __init__(self, rowptr, col, weight, phase):
-        self.rowptr, self.col, self.weight, self.phase = rowptr, col, weight, phase
+    def __init__(self, rowptr, col, weight, phase, other=None):
+        self.rowptr, self.col, self.weight, self.phase, self.other = rowptr, col, weight, phase, other
         self._cast = {}
 
     def coefficients(self, real):
@@ -95,11 +98,14 @@ class TransferPlan(object):
             out_sorted, by_out = order.values.contiguous(), order.indices
             col = r[by_out, 1].contiguous()
             w, ph = w[by_out].contiguous(), None if ph is None else ph[by_out].contiguous()
-            fwd = _Csr(torch.searchsorted(out_sorted, torch.arange(n_out + 1, device=dev)).to(torch.int32), col.to(torch.int32), w, ph)
             order = torch.sort(col, stable=True)          # the transposed matrix: grouped by `in`, a row's slots in the order above
             in_sorted, by_in = order.values.contiguous(), order.indices
+            slots = torch.arange(E, dtype=torch.int32, device=dev)
+            fwd = _Csr(torch.searchsorted(out_sorted, torch.arange(n_out + 1, device=dev)).to(torch.int32), col.to(torch.int32), w, ph,
+                       torch.empty_like(slots).index_put_((by_in,), slots))          # transposed slot t holds forward slot by_in[t]
             bwd = _Csr(torch.searchsorted(in_sorted, torch.arange(n_in + 1, device=dev)).to(torch.int32),
-                       out_sorted[by_in].to(torch.int32).contiguous(), w[by_in].contiguous(), None if ph is None else ph[by_in].contiguous())
+                       out_sorted[by_in].to(torch.int32).contiguous(), w[by_in].contiguous(), None if ph is None else ph[by_in].contiguous(),
+                       by_in.to(torch.int32).contiguous())
         self._set(fwd, bwd, n_out, n_in, E, conj_phase, dev)
 
     def _set(self, fwd, bwd, n_out, n_in, n_rows, conj_phase, device):
@@ -152,13 +158,8 @@ class _TangentTransfer(torch.autograd.Function):
         return _launch(g, plan.adjoint()), None          # d/dx of Re<gy, T x> is T^H gy: the same kernel on the transposed CSR
 
 
-def tangent_transfer(x, plan):
-    """y (n_out, C) = T x for x (n_in, C) complex64 / complex128 (coefficient weight * phase, or weight * conj(phase) for a plan
-    with conj_phase) or float32 / float64 (coefficient weight), on the plan's ROCm device.  One launch, no atomics: a row's terms
-    are added in the plan's slot order, two runs give the same bits, a row without terms is exactly zero.  Gradient flows to x
-    only (the same kernel on plan.adjoint(), as deterministic as the forward pass), and only when x requires one.  A
-    non-contiguous x is made contiguous."""
-    what = 'tangent_transfer'
+def _check_features(x, plan, what):
+    """the checks of (x, plan) that every operator on a plan makes before it launches"""
     if not isinstance(plan, TransferPlan):
         raise ValueError(f'{what}: plan must be a TransferPlan, got {type(plan).__name__}')
     if not torch.is_tensor(x) or x.dim() != 2:
@@ -173,7 +174,87 @@ def tangent_transfer(x, plan):
         raise ValueError(f'{what}: x must be ({plan.n_in}, C) with C >= 1 for this plan, got {tuple(x.shape)}')
     if plan.n_out * int(x.shape[1]) >= 2 ** 40 or int(x.shape[1]) >= 2 ** 31:
         raise ValueError(f'{what}: n_out * C must stay below 2^40, got {plan.n_out} x {int(x.shape[1])}')
+
+
+def tangent_transfer(x, plan):
+    """y (n_out, C) = T x for x (n_in, C) complex64 / complex128 (coefficient weight * phase, or weight * conj(phase) for a plan
+    with conj_phase) or float32 / float64 (coefficient weight), on the plan's ROCm device.  One launch, no atomics: a row's terms
+    are added in the plan's slot order, two runs give the same bits, a row without terms is exactly zero.  Gradient flows to x
+    only (the same kernel on plan.adjoint(), as deterministic as the forward pass), and only when x requires one.  A
+    non-contiguous x is made contiguous."""
+    _check_features(x, plan, 'tangent_transfer')
     return _TangentTransfer.apply(x, plan)
+
+
+class _TangentTransferMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, plan):
+        lib = _lib.load()
+        x = x.detach().resolve_conj().resolve_neg().contiguous()
+        dt, cplx = _DTYPES[x.dtype]
+        C = int(x.shape[1])
+        csr = plan._fwd
+        ph = csr.coefficients(_REAL[dt])[1] if cplx else None
+        with _on(x.device):
+            y = torch.empty((plan.n_out, C), dtype=x.dtype, device=x.device)
+            arg = torch.empty((plan.n_out, C), dtype=torch.int32, device=x.device)
+            _lib.check(lib.fc_transfer_max(_ptr(x), _ptr(csr.rowptr), _ptr(csr.col), _ptr(ph), int(plan.conj_phase and cplx), plan.n_out,
+                                           plan.n_in, plan.n_rows, C, dt, cplx, _ptr(y), _ptr(arg), _stream()), 'fc_transfer_max')
+        ctx.plan = plan
+        ctx.save_for_backward(arg)
+        ctx.mark_non_differentiable(arg)
+        return y, arg
+
+    @staticmethod
+    def backward(ctx, g, _):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        lib = _lib.load()
+        plan = ctx.plan
+        arg, = ctx.saved_tensors
+        g = g.detach().resolve_conj().resolve_neg().contiguous()
+        dt, cplx = _DTYPES[g.dtype]
+        C = int(g.shape[1])
+        csr = plan._bwd
+        ph = csr.coefficients(_REAL[dt])[1] if cplx else None
+        with _on(g.device):
+            gx = torch.empty((plan.n_in, C), dtype=g.dtype, device=g.device)
+            _lib.check(lib.fc_transfer_max_backward(_ptr(g), _ptr(arg), _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.other), _ptr(ph),
+                                                    int(plan.conj_phase and cplx), plan.n_out, plan.n_in, plan.n_rows, C, dt, cplx, _ptr(gx),
+                                                    _stream()), 'fc_transfer_max_backward')
+        return gx, None
+
+
+def tangent_transfer_max(x, plan, return_indices=False):
+    """y (n_out, C): max pooling by magnitude over the rows of a plan (csrc/fc_maxpool.hip), for x (n_in, C) complex64 / complex128 /
+    float32 / float64 on the plan's ROCm device.  Output row o takes, per channel, ONE of the plan's rows [o, i]:
+
+      key      of a complex entry: k = fl(fl(re * re) + fl(im * im)) in x's scalar type, every operation rounded on its own (numpy
+               gives the same bits).  |x| does not depend on a sample's frame, so the choice is gauge invariant.  Of a real entry:
+               k = x itself -- a plain max, not a magnitude max.
+      winner   the slot e* of output row o (the plan's slot order: rows grouped by out, the caller's order within a group) with the
+               largest key(x[in(e), c]); ties go to the smallest slot.  NaN features are outside the contract.
+      value    complex x: y[o, c] = u[e*] * x[in(e*), c] with u the row's phase (conj(phase) for a plan with conj_phase, 1 without
+               phases): the winner parallel-transported into the receiver's frame.  Real x: x[in(e*), c], copied bit for bit.
+
+    The plan's weights are NOT read: a max is not weighted, every row of the plan is a member.  A row of y without terms is
+    exactly zero.  With return_indices also (n_out, C) int64: the INPUT row in(e*) of every winner, -1 where there is none.
+    One launch forward and one backward, no atomics, the same bits on every run.  Gradient flows to x only, and only when x
+    requires one: gx[i, c] = the sum, over the outputs o that input i won, of conj(u) * gy[o, c] (real: gy[o, c]) in the transposed
+    plan's slot order; an input that won nowhere gets exactly zero.  A non-contiguous x is made contiguous.  Arguments are checked
+    as tangent_transfer checks them, before anything is launched."""
+    what = 'tangent_transfer_max'
+    _check_features(x, plan, what)
+    if not isinstance(return_indices, bool):
+        raise ValueError(f'{what}: return_indices must be True or False, got {return_indices!r}')
+    y, arg = _TangentTransferMax.apply(x, plan)
+    if not return_indices:
+        return y
+    with _on(x.device):
+        slot = arg.to(torch.int64)
+        if plan.n_rows == 0:
+            return y, slot
+        return y, torch.where(slot >= 0, plan._fwd.col.to(torch.int64)[slot.clamp(min=0)], slot)
 
 
 # ------------------------------------------------------------------ building a level pair

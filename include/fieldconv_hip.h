@@ -932,6 +932,62 @@ int fc_tangent_norm_backward(const void* x, const void* w, const int64_t* ptr, c
 int fc_knn_weights(const int32_t* rowptr, const int32_t* cand, const float* dist, int32_t n_f, int32_t n_slots, int32_t k, int32_t power,
                    int32_t* sel, float* weight, void* stream);
 
+/* ---- max pooling by magnitude: over the rows of a transfer plan and over the meshes of a batch (csrc/fc_maxpool.hip) ----------- *
+ * key     of a complex entry z: k = fl(fl(re * re) + fl(im * im)) in z's scalar type (float32 for complex64, float64 for
+ *         complex128), every operation rounded on its own, no fused multiply-add: numpy gives the same bits.  |z| does not depend
+ *         on the frame z is written in.  Of a real entry: k = x itself, a plain max and not a magnitude max.
+ * winner  among candidates (k, s), s the slot (transfer) or the row number (meshes): the largest k wins, ties go to the smallest s.
+ *         A candidate replaces the incumbent iff k_new > k_old, or k_new == k_old and s_new < s_old.  This is a total order: the
+ *         result does not depend on how the candidates are split over lanes, wavefronts or launches.  NaN features are outside
+ *         the contract: the winner is then meaningless, but nothing is read or written outside the buffers.
+ * No atomics: every output element is owned by one lane, the same bits on every run.  No allocation or synchronisation inside.
+ * Alignment: every feature and gradient buffer (x, y, grad_y, grad_x, out, grad_out, partial_key) starts on a multiple of the size of
+ *         one of its entries -- 4 bytes for float32, 8 for float64 and complex64, 16 for complex128 -- and every int32 / int64 array
+ *         on a multiple of its element's size; rows are dense, so every entry is then aligned.  This is not checked.  Only the
+ *         float32 path of fc_transfer_max* asks for more when it can use it: with C even and x, y, arg (grad_y, grad_x, arg) on
+ *         8-byte boundaries it moves two channels per lane, else one.
+ *
+ * fc_transfer_max            x (n_in, C), y (n_out, C), rowptr / col, phase, conj_phase, dtype, is_complex as in fc_transfer; there is
+ *         NO weight: a max is not weighted and every slot of a row is a member.  For output row o and channel c the candidates are
+ *         the slots e in [rowptr[o], rowptr[o+1]) with key(x[col[e], c]); with e* the winner, arg[o, c] = e* (arg: (n_out, C) int32)
+ *         and y[o, c] = u[e*] * x[col[e*], c] for complex x, u = phase[e] (conj(phase[e]) when conj_phase is 1, 1 when phase is
+ *         NULL): the winner's value parallel-transported into the receiver's frame; y[o, c] = x[col[e*], c], copied bit for bit, for
+ *         real x (phase and conj_phase are not read).  rowptr entries are clamped to [0, n_slots]; a slot whose col lies outside
+ *         [0, n_in) is no candidate and reads nothing.  A row without a usable slot gives y = 0 exactly and arg = -1.  A row may
+ *         have any number of slots.  One launch.
+ * fc_transfer_max_backward   on the TRANSPOSED CSR of the same plan: rowptr_t (n_in+1) / col_t (n_slots; the OUTPUT row of a slot) /
+ *         phase_t (n_slots, or NULL) and slot_t (n_slots) int32, the slot number in the forward CSR of every transposed slot;
+ *         conj_phase as given to the forward call.  grad_x[i, c] = the sum over the slots t of transposed row i, added to a zero in
+ *         ascending order, with arg[col_t[t], c] == slot_t[t], of conj(u[t]) * grad_y[col_t[t], c] (real x: grad_y[col_t[t], c]
+ *         alone).  An input that won nowhere gets exactly zero.  rowptr_t is clamped as above; a slot whose col_t lies outside
+ *         [0, n_out) is skipped; arg and slot_t are only compared.  One launch.
+ *
+ * fc_segment_max_forward     x (N, C), ptr (B+1 int64, DEVICE memory, clamped to [0, N] by the kernels), dtype as in the per-mesh
+ *         pooling section; is_complex 1 (interleaved pairs) or 0.  For mesh b and channel c the candidates are the rows
+ *         n = ptr[b] .. ptr[b+1] - 1 with key(x[n, c]) and s = n; with n* the winner, index[b, c] = n* (index: (B, C) int32) and
+ *         out[b, c] (real, (B, C)) = softAbs(x[n*, c]) for complex x -- sqrt(k) outside the origin box, 0 inside (reference
+ *         utils/field.py:29-37, fc_soft_abs_forward's rule); |x| is never written per row -- or x[n*, c] bit for bit for real x.
+ *         It is the softAbs of the entry of largest key, not the largest softAbs: softAbs is not monotone in |x| at the corner of the
+ *         origin box.  An empty mesh gives out = 0 and index = -1.  Two launches: the partial winners (key, row) of every chunk of
+ *         64 rows counted from a mesh's first row, then one combination per mesh over its chunks, both in the (k, s) order: the
+ *         result equals a plain argmax whatever the chunking, and a mesh gets the same bits alone and inside a batch.  The partial
+ *         buffers are caller-owned and need not be initialised: partial_key, N / 64 + B (integer division) rows of C scalars of
+ *         dtype, and partial_row, as many rows of C int32 -- the chunk slots of the per-mesh pooling section, at least
+ *         sum_b ceil(n_b / 64), known without reading ptr.
+ * fc_segment_max_backward    one launch, every (n, c) written by its own thread: grad_x[n, c] = grad_out[b, c] * x / |x| outside the
+ *         origin box and 0 inside (fc_soft_abs_backward's rule) where n == index[b, c], b the mesh of row n, and 0 everywhere else;
+ *         for real x grad_x[n, c] = grad_out[b, c] there (x is not read and may be NULL).  grad_out (B, C) real, grad_x like x.
+ * Limits of both: N >= 0, B >= 1, 1 <= C <= 64 * 65535, N + 64 B < 2^31, else FC_ERR_BAD_ARGUMENT. */
+int fc_transfer_max(const void* x, const int32_t* rowptr, const int32_t* col, const void* phase, int32_t conj_phase, int32_t n_out,
+                    int32_t n_in, int32_t n_slots, int32_t C, int32_t dtype, int32_t is_complex, void* y, int32_t* arg, void* stream);
+int fc_transfer_max_backward(const void* grad_y, const int32_t* arg, const int32_t* rowptr_t, const int32_t* col_t, const int32_t* slot_t,
+                             const void* phase_t, int32_t conj_phase, int32_t n_out, int32_t n_in, int32_t n_slots, int32_t C, int32_t dtype,
+                             int32_t is_complex, void* grad_x, void* stream);
+int fc_segment_max_forward(const void* x, const int64_t* ptr, int32_t N, int32_t B, int32_t C, int32_t dtype, int32_t is_complex, void* out,
+                           int32_t* index, void* partial_key, int32_t* partial_row, void* stream);
+int fc_segment_max_backward(const void* x, const void* grad_out, const int32_t* index, const int64_t* ptr, int32_t N, int32_t B, int32_t C,
+                            int32_t dtype, int32_t is_complex, void* grad_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
