@@ -235,6 +235,7 @@ __global__ __launch_bounds__(kEchoWaves * kWave) void echo_backward_kernel(
 }
 
 // wavefronts per vertex: spread large supports over the workgroup when the mesh alone cannot fill the chip
+// (tests/_lift_echo_cases.py restates this rule and tests/test_lift_echo_host.py pins the restatement to the text of this function)
 static int echo_waves_per_vertex(int N, int E) {
     static const int forced = [] { const char* e = dev_env("FC_ECHO_WPV"); return e ? atoi(e) : 0; }();       // development, read once
     if (forced) return forced;

@@ -112,7 +112,7 @@ __global__ void tfg_combine_kernel(const Cx<T>* __restrict__ ang, const T* __res
 }
 
 // adjoint of the combination per (n, o, i): GA = dL/dA (complex), GM = dL/dM, GP = dL/dphase contribution
-//   y = rho E, rho = |M|, E = u c:  g_rho = Re(conj(gy) E), GM = g_rho sign(M) (softAbsolute: -1 below zero, +1 otherwise);
+//   y = rho E, rho = |M|, E = u c:  g_rho = Re(conj(gy) E), GM = g_rho sign(M) (softAbsolute: -1 below zero, +1 above; 0 at exactly zero, where torch.polar passes no magnitude gradient);
 //   GP = rho Re(conj(gy) i E) = -rho Im(conj(gy) E);  g_u = rho gy conj(c);  u = A/|A|: GA = i u Im(conj(u) g_u) / |A| (0 inside the box)
 template <typename T>
 __global__ void tfg_adjoint_kernel(const Cx<T>* __restrict__ ang, const T* __restrict__ mag, const T* __restrict__ zA,
@@ -131,7 +131,7 @@ __global__ void tfg_adjoint_kernel(const Cx<T>* __restrict__ ang, const T* __res
     const Cx<T> g = gy[no];
     const Cx<T> ge = mul_conj(E, g);                  // E conj(gy): Re = Re(conj(gy) E), Im = Im(conj(gy) E)
     const T rho = M < 0 ? -M : M;
-    GM[idx] = ge.x * (M < 0 ? (T)-1 : (T)1);
+    GM[idx] = ge.x * (M < 0 ? (T)-1 : (M > 0 ? (T)1 : (T)0));       // (torch.polar: no magnitude gradient where rho is exactly zero)
     GP[idx] = -rho * ge.y;
     Cx<T> ga = cx<T>(0, 0);
     if (live) {

@@ -240,7 +240,9 @@ __global__ __launch_bounds__(kTfWaves * kWave) void trans_field_backward_vertex_
                 const float rho = fabsf(M);
                 const float g_rho = g.x * E.x + g.y * E.y;                      // Re(conj(g) E)
                 const float g_phi = rho * (g.y * E.x - g.x * E.y);              // Re(conj(g) i rho E)
-                const float gM = M < 0.f ? -g_rho : g_rho;                      // softAbsolute (reference utils/field.py:18-26)
+                // softAbsolute (reference utils/field.py:18-26) under torch.polar, whose magnitude gradient is Re(conj(g) sgn(result)): none
+                // where rho is exactly zero (a vertex whose in-neighbours all carry x = 0)
+                const float gM = M < 0.f ? -g_rho : (M > 0.f ? g_rho : 0.f);
                 // angle(A): g_A = g_phi * i A / |A|^2 ; none inside the origin box
                 const float sA = orgA ? 0.f : g_phi * inv * inv;
                 const float2 gA = make_float2(-A.y * sA, A.x * sA);
@@ -379,6 +381,7 @@ __global__ __launch_bounds__(kTfWaves * kWave) void trans_field_backward_input_k
     }
 }
 
+// (tests/_lift_echo_cases.py restates this rule and tests/test_lift_echo_host.py pins the restatement to the text of this function)
 static int tf_waves_per_vertex(int N, int E) {
     const long deg = N > 0 ? (long)E / N : 0;
     if (deg >= 64 && N < 65536) return 4;

@@ -83,7 +83,7 @@ def rowwise_err(a, ref):
     num = np.abs(a - ref).max(axis=1)
     den = np.abs(ref).max(axis=1)
     assert np.all(num[den == 0] == 0)
-    return float((num[den > 0] / den[den > 0]).max())
+    return float((num[den > 0] / den[den > 0]).max(initial=0.0))
 
 
 def row_max(t):

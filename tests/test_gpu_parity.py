@@ -965,14 +965,8 @@ def test_echo_kernels_vs_host_composite(dev, N, k, C, n_bins):
     # The reference's votes vanish at exactly integer raster coordinates (ceil == floor, nn/echo.py:30-61): a coordinate that
     # rounds to an integer in fp32 but sits 1e-7 beside it in float64 drops a whole vote (about once per 1e6 (edge, channel)
     # pairs, tools/fuzz/fuzz_components.py).  Entries fed by such a vote are not comparable and are left out.
-    frame = torch.conj(torch.polar(torch.ones(N, C, dtype=torch.float64), torch.angle(x.to(torch.complex128))))
-    qq = torch.view_as_real((ln * 0.999).to(torch.complex128)[:, None] * frame[edges[:, 0]] * n_bins)
-    near = ((qq - torch.round(qq)).abs() < 1e-5).any(dim=2) & (ln.abs() > 0)[:, None]
-    cols = torch.arange(C)[None, :].expand(edges.shape[0], -1)
-    fragile = torch.zeros(N, C, dtype=torch.bool)
-    fragile[edges[:, 1][:, None].expand(-1, C)[near], cols[near]] = True
-    tainted = torch.zeros(N, dtype=torch.bool)
-    tainted[edges[:, 0][fragile.any(dim=1)[edges[:, 1]]]] = True
+    from _lift_echo_cases import fragile_votes          # (the mask computation lives with the row-wise ECHO cases)
+    fragile, tainted = fragile_votes(x.to(torch.complex128), edges, (ln * 0.999).to(torch.complex128), n_bins)
     ok, okg = (~fragile)[..., None].numpy(), (~tainted)[:, None].numpy()
     assert float(fragile.float().mean()) < 1e-2
     assert rel_err(H(dd) * ok, dr.detach().numpy() * ok) < 5e-6             # measured 1-3e-7
