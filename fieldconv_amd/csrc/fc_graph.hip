@@ -66,16 +66,35 @@ __global__ __launch_bounds__(kAnalyzeEdges) void graph_analyze_kernel(
     int q = 0;
     if (sten) {
         const float2* row = rows + threadIdx.x * (R * F + 1);
+        // The magnitudes that are compared with each other below are SQUARED ones, so the row is first brought to unit size by a
+        // power of two (exact): a valid row of entries below 2^-63 would otherwise square to zero, read as "all rings empty" and
+        // come out factored with w_q = w_{q+1} = 0 -- a convolution of zeros, and no error.  Whether a ring is empty is asked of
+        // the entries themselves (any component non-zero), never of a square.  graph.py: factor_stencil does both the same way.
+        // The records keep the phases at their own size.  A row with an infinite or NaN entry has no factorisation: flag 1.
+        float amax = 0.f;
+        bool finite = true;
+        for (int k = 0; k < R * F; ++k) {
+            const float2 z = row[k];
+            finite = finite && isfinite(z.x) && isfinite(z.y);
+            amax = fmaxf(amax, fmaxf(fabsf(z.x), fabsf(z.y)));
+        }
+        int ex = 0;
+        if (finite && amax > 0.f) (void)frexpf(amax, &ex);
+        const auto unit = [ex](float2 z) { return make_float2(ldexpf(z.x, -ex), ldexpf(z.y, -ex)); };
         // ring magnitudes: first non-zero ring, nothing outside {q, q+1}
-        float mag[kGraphMaxR];
+        float mag[kGraphMaxR];          // largest |component| of the ring, at the row's own size: only compared with 0
         float scale = 0.f;
 #pragma unroll
         for (int r = 0; r < kGraphMaxR; ++r) {
             mag[r] = 0.f;
             if (r < R) {
-                float m2 = 0.f;
-                for (int f = 0; f < F; ++f) m2 = fmaxf(m2, cabs2(row[r * F + f]));
-                mag[r] = m2;
+                float m1 = 0.f, m2 = 0.f;
+                for (int f = 0; f < F; ++f) {
+                    const float2 z = row[r * F + f];
+                    m1 = fmaxf(m1, fmaxf(fabsf(z.x), fabsf(z.y)));
+                    m2 = fmaxf(m2, cabs2(unit(z)));
+                }
+                mag[r] = m1;
                 scale = fmaxf(scale, m2);
             }
         }
@@ -86,29 +105,31 @@ __global__ __launch_bounds__(kAnalyzeEdges) void graph_analyze_kernel(
         for (int r = 0; r < kGraphMaxR; ++r)
             if (r < R && !found && mag[r] > 0.f) { first = r; found = true; }
         q = min(first, R - 2);
-        bool bad = false;
+        bool bad = !finite;
 #pragma unroll
         for (int r = 0; r < kGraphMaxR; ++r)
             if (r < R && mag[r] > 0.f && (r < q || r > q + 1)) bad = true;
-        float2 s0[kGraphMaxF], s1[kGraphMaxF], ph[kGraphMaxF];
+        float2 s0[kGraphMaxF], s1[kGraphMaxF], ph[kGraphMaxF], phu[kGraphMaxF];       // phu: the phases of the unit-size row
         float den = 0.f, n0 = 0.f, n1 = 0.f;
 #pragma unroll
         for (int f = 0; f < kGraphMaxF; ++f)
             if (f < F) {
-                s0[f] = row[q * F + f];
-                s1[f] = row[(q + 1) * F + f];
-                ph[f] = make_float2(s0[f].x + s1[f].x, s0[f].y + s1[f].y);       // = phase * (w_q + w_{q+1})
-                den += cabs2(ph[f]);
-                n0 += s0[f].x * ph[f].x + s0[f].y * ph[f].y;                      // Re(s0 conj(ph))
-                n1 += s1[f].x * ph[f].x + s1[f].y * ph[f].y;
+                const float2 r0 = row[q * F + f], r1 = row[(q + 1) * F + f];
+                ph[f] = make_float2(r0.x + r1.x, r0.y + r1.y);                    // = phase * (w_q + w_{q+1})
+                s0[f] = unit(r0);
+                s1[f] = unit(r1);
+                phu[f] = make_float2(s0[f].x + s1[f].x, s0[f].y + s1[f].y);
+                den += cabs2(phu[f]);
+                n0 += s0[f].x * phu[f].x + s0[f].y * phu[f].y;                    // Re(s0 conj(ph))
+                n1 += s1[f].x * phu[f].x + s1[f].y * phu[f].y;
             }
         const float w0 = den > 0.f ? n0 / den : 0.f, w1 = den > 0.f ? n1 / den : 0.f;
         float err2 = 0.f;
 #pragma unroll
         for (int f = 0; f < kGraphMaxF; ++f)
             if (f < F) {
-                err2 = fmaxf(err2, cabs2(make_float2(s0[f].x - w0 * ph[f].x, s0[f].y - w0 * ph[f].y)));
-                err2 = fmaxf(err2, cabs2(make_float2(s1[f].x - w1 * ph[f].x, s1[f].y - w1 * ph[f].y)));
+                err2 = fmaxf(err2, cabs2(make_float2(s0[f].x - w0 * phu[f].x, s0[f].y - w0 * phu[f].y)));
+                err2 = fmaxf(err2, cabs2(make_float2(s1[f].x - w1 * phu[f].x, s1[f].y - w1 * phu[f].y)));
             }
         if (bad || sqrtf(err2) > kGraphTol * scale) atomicOr(flags, 1);
         float* rp = rec + (size_t)e * a.recf;
@@ -126,25 +147,26 @@ __global__ __launch_bounds__(kAnalyzeEdges) void graph_analyze_kernel(
             float2 c = make_float2(0.f, 0.f), g = make_float2(1.f, 0.f);
             if (B >= 1) {
                 c = ph[B];
-                const float cm2 = cabs2(c);
+                const float2 cu = phu[B];
+                const float cm2 = cabs2(cu);
                 const bool live = cm2 > 0.f;
                 if (live) {
-                    const float2 n = ph[B + 1];
-                    g = make_float2((n.x * c.x + n.y * c.y) / cm2, (n.y * c.x - n.x * c.y) / cm2);      // ph[B+1] / c
+                    const float2 n = phu[B + 1];
+                    g = make_float2((n.x * cu.x + n.y * cu.y) / cm2, (n.y * cu.x - n.x * cu.y) / cm2);      // ph[B+1] / c
                 }
                 float pscale = 0.f;
 #pragma unroll
                 for (int f = 0; f < kGraphMaxF; ++f)
-                    if (f < F) pscale = fmaxf(pscale, cabs2(ph[f]));
+                    if (f < F) pscale = fmaxf(pscale, cabs2(phu[f]));
                 pscale = sqrtf(pscale);
                 float err = fabsf(sqrtf(cabs2(g)) - 1.f) * sqrtf(cm2);
-                float2 p = c, pc = c;
+                float2 p = cu, pc = cu;
 #pragma unroll
                 for (int m = 1; m <= (kGraphMaxF - 1) / 2; ++m)
                     if (m <= B) {
                         p = cmul(p, g);
                         pc = cmul_conj(pc, g);
-                        const float2 up = ph[B + m], dn = ph[B - m];
+                        const float2 up = phu[B + m], dn = phu[B - m];
                         err = fmaxf(err, sqrtf(cabs2(make_float2(up.x - p.x, up.y - p.y))));
                         err = fmaxf(err, sqrtf(cabs2(make_float2(dn.x - pc.x, dn.y - pc.y))));
                     }

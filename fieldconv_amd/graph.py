@@ -39,8 +39,21 @@ def factor_stencil(sten, tol=2e-6):
     stencils simply stay on the dense kernels.  One host synchronisation (the verdict)."""
     E, R, F = sten.shape
     B = (F - 1) // 2
-    mag = sten.abs().amax(dim=2)                                   # (E,R)
-    nz = mag > 0
+    # Rows at unit size (times a power of two: exact) for every comparison of magnitudes below, as graph_analyze_kernel has them:
+    # the squared magnitudes of a valid row of entries below 2^-63 would underflow.  The factor 2^-ex goes on in two halves, each a
+    # normal float32 whatever the row holds (denormal rows, rows near the largest float): two more passes over the (E,R,F) stencil,
+    # on a path that only CPU tensors and the tests take.  Whether a ring is empty is asked of the entries themselves (any component
+    # non-zero), as in the kernel.  The records keep the phases at their own size.  Rows with inf or NaN entries do not factor.
+    full = sten
+    comp = torch.view_as_real(sten).abs()
+    amax = comp.amax(dim=(1, 2, 3))
+    finite = torch.isfinite(amax)
+    _, ex = torch.frexp(torch.where(finite & (amax > 0), amax, torch.ones_like(amax)))
+    half = torch.div(ex, 2, rounding_mode='floor')
+    one = torch.ones_like(amax)
+    sten = (sten * torch.ldexp(one, -half)[:, None, None]) * torch.ldexp(one, half - ex)[:, None, None]
+    mag = sten.abs().amax(dim=2)                                   # (E,R), unit size
+    nz = comp.amax(dim=(2, 3)) > 0
     first = torch.argmax(nz.to(torch.int8), dim=1)                 # first non-zero ring, 0 if the row is empty
     q = torch.clamp(first, max=R - 2)
     ring = torch.arange(R, device=sten.device)[None, :]
@@ -57,7 +70,7 @@ def factor_stencil(sten, tol=2e-6):
     w1 = torch.where(den > 0, w1, torch.zeros_like(w1))
     err = torch.maximum((s0 - w0[:, None] * ph).abs().amax(1), (s1 - w1[:, None] * ph).abs().amax(1))
     scale = mag.amax(1)
-    bad = outside.any() | (err > tol * scale).any()
+    bad = outside.any() | (err > tol * scale).any() | (~finite).any()
     if bool(bad):
         return None
     recf = (4 + 2 * F + 3) // 4 * 4
@@ -65,6 +78,7 @@ def factor_stencil(sten, tol=2e-6):
     rec[:, 0] = q.to(torch.int32).view(torch.float32)
     rec[:, 1] = w0
     rec[:, 2] = w1
+    ph = full[rows, q] + full[rows, q + 1]
     rec[:, 4:4 + 2 * F] = torch.view_as_real(ph.contiguous()).reshape(E, 2 * F)
     return rec
 
