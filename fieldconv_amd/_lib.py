@@ -224,6 +224,12 @@ SIGNATURES = {
                                               ctypes.c_float, _c_int32, _vp, _vp, _sz, _vp]),
     'fc_geodesic_ball_fill': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _vp, _c_int32, _c_int32, _vp, _c_int32, _c_int32, _c_int32,
                                              ctypes.c_float, _c_int32, _vp, ctypes.c_int64, _vp, _vp, _vp, _sz, _vp]),
+    'fc_geodesic_fps_among': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _c_int32, _c_int32, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp,
+                                             _vp, _vp, _vp, _sz, _vp]),
+    'fc_geodesic_ball_count_at': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _vp, _c_int32, _c_int32, _vp, _c_int32, _vp, _c_int32,
+                                                 _c_int32, _c_int32, ctypes.c_float, _c_int32, _vp, _vp, _sz, _vp]),
+    'fc_geodesic_ball_fill_at': (ctypes.c_int, [_vp, _vp, _vp, _c_int32, _c_int32, _vp, _vp, _c_int32, _c_int32, _vp, _c_int32, _vp, _c_int32,
+                                                _c_int32, _c_int32, ctypes.c_float, _c_int32, _vp, ctypes.c_int64, _vp, _vp, _vp, _sz, _vp]),
     'fc_logmap_ball_lds_vertices': (_c_int32, []),
     'fc_vertex_frames': (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_int32, _c_int32, _vp, _vp, _vp, _vp]),
     'fc_logmap_workspace_bytes': (_sz, [_c_int32, _c_int32, _c_int32]),

@@ -416,7 +416,7 @@ def interpolation_plan(pos, face, sample_idx, coarse, k=3, power=2, radius=None,
             on one) and the plan is [f, cell[f]] with weight 1 and phase 1.  Given: a finite number > 0.
     candidates   every pair (c, f) with d_a[sample_idx[f]] < fl32(radius), strict, d_a the single-source field of vertex
             a = sample_idx[coarse[c]] bounded by radius: geodesic_radius_edges' relation, coarse queries only, never truncated.
-            (All S_f balls are solved and the coarse ones kept: a restriction of the ball search to some queries does not exist.)
+            (Only the S_c coarse balls are solved: geodesic_radius_edges(..., queries=coarse).)
     rows    [coarse[c], f] go through log_map_transport(..., bound=radius): dist is its logMag, the distance the convolution
             sees, xp its phase.  Every row is reached by construction; that is checked.
     plan    per fine sample f its candidates ascending in c go to knn_weights(k, power); its m = min(k, candidates) rows [f, c_i]
@@ -466,12 +466,9 @@ def interpolation_plan(pos, face, sample_idx, coarse, k=3, power=2, radius=None,
             xp = torch.ones(int(f.numel()), dtype=torch.complex64, device=dev)
         else:
             edges = geodesic_radius_edges(pos, face, sample_idx, radius, max_num_neighbors=S_f, pos_ptr=pos_ptr, sample_ptr=ptr,
-                                          graph=graph).to(dev)          # S_f neighbours at most: the cap cannot bite
-            where = torch.full((S_f,), -1, dtype=torch.int64, device=dev)
-            where[coarse.to(dev)] = torch.arange(S_c, device=dev)
-            c = where[edges[:, 0]]
-            keep = c >= 0
-            c, a, f = c[keep], edges[keep, 0], edges[keep, 1]
+                                          graph=graph, queries=coarse).to(dev)          # S_f neighbours at most: the cap cannot bite
+            a, f = edges[:, 0], edges[:, 1]
+            c = torch.searchsorted(coarse.to(dev).contiguous(), a.contiguous())          # (coarse ascends: a's place in it)
             if int(f.numel()):
                 mag, _, xp, reached = log_map_transport(pos, face, sample_idx, torch.stack((a, f), 1), radius, graph=graph, pos_ptr=pos_ptr,
                                                         ptr=ptr, return_reached=True)

@@ -798,6 +798,21 @@ int fc_segment_sum_f32(const float* x, const int64_t* ptr, int64_t N, int32_t K,
  *                    device memory and n_edges = offsets[S]; fill solves the queries again and writes edges (n_edges,2) int64
  *                    and, unless null, edge_dist (n_edges) float32: the bits of fc_geodesic_rows' row q.  Workspace: when
  *                    max_range exceeds the LDS capacity, one slot per query of the launch (the query below), else 0.
+ * fps_among          fps with the choice restricted to candidates: candidate (V) uint8 in device memory, in the union's vertex
+ *                    numbering, nonzero where the vertex may be taken.  idx[.. + 0] = start[b] (taken first even where it is no
+ *                    candidate: the caller forbids that); sample k+1 is the CANDIDATE not yet taken with the largest d_k, and
+ *                    d_k is still the field of the first k+1 samples over the whole mesh: every vertex relaxes, candidate or
+ *                    not.  +inf first, ties to the lowest vertex, no vertex twice, as above; with every vertex a candidate the
+ *                    result is fps's, index for index and bit for bit.  n_samples[b] may exceed the candidates of mesh b: once
+ *                    none is free the remaining slots of the mesh hold -1 and dist is the field of what was taken.  Workspace
+ *                    and errors as fps (fc_geodesic_fps_workspace_bytes); a null candidate is FC_ERR_BAD_ARGUMENT.
+ * ball count_at /    ball count / fill for a LIST of queries: query_pos (Q) int64 in device memory, positions in sample_idx
+ * fill_at            (ascending, checked by the caller, so that the rows come grouped as above); list slot s, for
+ *                    q0 <= s < q0 + nq <= Q, solves query q = query_pos[s] and is skipped, with count 0, where q is outside
+ *                    [0,S).  count (Q) and offsets (Q+1) are indexed by the list slot; the rows are [q, j], and bound, strict
+ *                    threshold and truncation to K are those of the query q above: the rows of ball fill whose column 0 is in
+ *                    the list.  Workspace: fc_geodesic_ball_workspace_bytes(max_range, nq), one slot per list slot of the
+ *                    launch.  Q >= 1; a null query_pos is FC_ERR_BAD_ARGUMENT.
  * max_range as above: the largest range; the kernels clamp what they read from the tables.  V, E, S < 2^31.  FC_ERR_WORKSPACE
  * when a workspace is missing or smaller.  No allocation or synchronisation inside. */
 int32_t fc_geodesic_fps_lds_vertices(void);
@@ -813,6 +828,18 @@ int fc_geodesic_ball_fill(const int32_t* rowptr, const int32_t* nbr, const float
                           const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S, int32_t q0,
                           int32_t nq, float epsilon, int32_t K, const int64_t* offsets, int64_t n_edges, int64_t* edges, float* edge_dist,
                           void* workspace, size_t workspace_bytes, void* stream);
+int fc_geodesic_fps_among(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                          int32_t B, int32_t max_range, const uint8_t* candidate, const int64_t* n_samples, const int64_t* start,
+                          const int64_t* out_ptr, int64_t total_out, int64_t* idx, float* dist, int64_t* sweeps, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int fc_geodesic_ball_count_at(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                              const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S,
+                              const int64_t* query_pos, int32_t Q, int32_t q0, int32_t nq, float epsilon, int32_t K, int32_t* count,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int fc_geodesic_ball_fill_at(const int32_t* rowptr, const int32_t* nbr, const float* length, int32_t V, int32_t E, const int64_t* pos_ptr,
+                             const int64_t* sample_ptr, int32_t B, int32_t max_range, const int64_t* sample_idx, int32_t S,
+                             const int64_t* query_pos, int32_t Q, int32_t q0, int32_t nq, float epsilon, int32_t K, const int64_t* offsets,
+                             int64_t n_edges, int64_t* edges, float* edge_dist, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- log map and parallel transport by the discrete exponential map (csrc/fc_logmap.hip) ----------------------------------- *
  * Schmidt, Grimm, Wyvill 2006 over the edge-graph metric of the sections above; not the Vector Heat Method of the reference's
