@@ -44,6 +44,17 @@ SHAPES = {
     'stream3100': (3100, 8, 16, 32, 1, 4),      # smallest streaming geometry
     'stream3075': (3075, 16, 64, 64, 3, 6),     # two walks, the k range in halves
 }
+# further shapes on the same generator, registered by sibling case modules (_wide_runtime_cases.py); kept apart from SHAPES so that
+# the tests that sweep SHAPES keep their cases.  EXTRA_MESHES: name -> function(name) returning what mesh() returns, for shapes whose
+# stencil is not FCPrecomp's.
+EXTRA_SHAPES = {}
+EXTRA_MESHES = {}
+
+
+def dims(name):
+    return SHAPES[name] if name in SHAPES else EXTRA_SHAPES[name]
+
+
 SMALLEST = 'split60'
 STREAMING_SHAPES = ('ring4400', 'stream3100', 'stream3075')         # N >= 3072: the streaming backward in the default mode
 CONTAINMENT_SHAPES = ('ring4400', 'stream3100', 'split60')          # ring forward + streaming backward, streaming backward, edge split
@@ -110,7 +121,9 @@ def mesh(name):
     """(edges (E,2) int64, sten (E,R,F) complex64) as numpy, built on the CPU; vertex N-2 has no out-edges, vertex 37 no in-edges."""
     from fieldconv_amd.data import sphere_support
     from oracle.torch_composites import FCPrecomp
-    N, k, I, O, B, R = SHAPES[name]
+    if name in EXTRA_MESHES:
+        return EXTRA_MESHES[name](name)
+    N, k, I, O, B, R = dims(name)
     no_out, no_in = N - 2, 37
     data = sphere_support(N, k=k, seed=N + k, support='p95')
     keep = (data.supp_edges[:, 0] != no_out) & (data.supp_edges[:, 1] != no_in)
@@ -127,14 +140,14 @@ ZERO_X_ROW, ZERO_W_ROW, ZERO_W_COL = 7, 3, 5
 
 def special_rows(name):
     """Rows that carry the planted origin-box entries (pinned to the smallest a_j): one per quarter of the mesh."""
-    N = SHAPES[name][0]
+    N = dims(name)[0]
     return np.array([1, N // 4 + 2, N // 2 + 3, (3 * N) // 4 + 5])
 
 
 @functools.lru_cache(maxsize=None)
 def base(name):
     """x0 (N,I), gy0 (N,O), W0 (O,I,R,F) complex64, and the module parameters of the three filter types (float32)."""
-    N, k, I, O, B, R = SHAPES[name]
+    N, k, I, O, B, R = dims(name)
     F = 2 * B + 1
     rng = np.random.default_rng([N, k, I, O])
     cplx = lambda *s: (rng.standard_normal(s) + 1j * rng.standard_normal(s)).astype(np.complex64)
@@ -166,7 +179,7 @@ def base(name):
 @functools.lru_cache(maxsize=None)
 def exponents(name, layout):
     """(a (N,), d (N,), b (O,), c (I,)) integer exponents of one layout."""
-    N, k, I, O, B, R = SHAPES[name]
+    N, k, I, O, B, R = dims(name)
     if layout in PERTURBED_LAYOUTS:
         a, d, b, c = exponents(name, PERTURBED_LAYOUTS[layout])
         a, d = a.copy(), d.copy()
@@ -219,7 +232,7 @@ def filter_of(name, layout, wkind):
     if wkind == 'explicit':
         return scaled_inputs(name, layout, 0, 0)[2].astype(np.complex128)
     z, s, p = scaled_params(name, layout, wkind)
-    return orc.effective_filter(z.astype(np.float64), s.astype(np.float64), p.astype(np.float64), wkind, SHAPES[name][4])
+    return orc.effective_filter(z.astype(np.float64), s.astype(np.float64), p.astype(np.float64), wkind, dims(name)[4])
 
 
 LIN_SHIFT = -200
@@ -287,14 +300,14 @@ def errors(name, layout, got, ref):
 def perturbed_set(name):
     """About 1 % of the vertices: the LAST vertex of every sixth tile, so that the row that directly follows it starts the next tile
     and the rest of its own tile lies in front of it."""
-    N = SHAPES[name][0]
+    N = dims(name)[0]
     P = np.arange(TILE - 1, N - 1, 6 * TILE)
     return P[~np.isin(P, [ZERO_X_ROW, mesh(name)[2], mesh(name)[3]] + list(special_rows(name)))]
 
 
 def affected_rows(name, P):
     """(y rows with an in-edge from P, gx rows with an out-edge into P or in P) as boolean masks."""
-    N = SHAPES[name][0]
+    N = dims(name)[0]
     edges = mesh(name)[0]
     inP = np.zeros(N, bool)
     inP[P] = True

@@ -133,7 +133,7 @@ def test_tiny_cotangents_reach_the_underflow_of_the_squared_inverse_scale(name, 
 
 @pytest.mark.parametrize('name', drc.CONTAINMENT_SHAPES + ('stream3075',))
 def test_containment_sets(name):
-    N = drc.SHAPES[name][0]
+    N = drc.dims(name)[0]
     P = drc.perturbed_set(name)
     assert 0 < P.size <= max(1, round(0.02 * N)) and np.all(P % drc.TILE == drc.TILE - 1)
     inP = np.zeros(N, bool)
