@@ -246,6 +246,11 @@ SIGNATURES = {
     'fc_transfer_max_backward': (ctypes.c_int, [_vp] * 6 + [_c_int32] * 7 + [_vp, _vp]),
     'fc_segment_max_forward': (ctypes.c_int, [_vp, _vp] + [_c_int32] * 5 + [_vp] * 5),
     'fc_segment_max_backward': (ctypes.c_int, [_vp] * 4 + [_c_int32] * 5 + [_vp, _vp]),
+    'fc_philox_words': (ctypes.c_int, [ctypes.c_uint64] * 3 + [ctypes.c_int64, _vp, _vp]),
+    'fc_dropout': (ctypes.c_int, [_vp, _vp] + [_c_int32] * 5 + [_vp, _c_int32, ctypes.c_uint32, ctypes.c_double, ctypes.c_uint64, ctypes.c_int64,
+                                  _vp, _vp]),
+    'fc_mesh_affine_draw': (ctypes.c_int, [_c_int32, ctypes.c_uint64, ctypes.c_int64, _vp, _c_int32] + [ctypes.c_float] * 5 + [_vp] * 3),
+    'fc_mesh_affine_apply': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),
 }
 
 _LIB = None

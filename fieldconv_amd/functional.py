@@ -1140,3 +1140,5 @@ from .logmap import log_map_transport, vertex_frames          # noqa: E402,F401 
 from .transfer import TransferPlan, level_transfer, sample_cells, tangent_transfer, tangent_transfer_max          # noqa: E402,F401  (csrc/fc_transfer.hip, fc_maxpool.hip)
 from .transfer import interpolation_plan, knn_weights, vertex_interpolation          # noqa: E402,F401  (csrc/fc_interp.hip)
 from .norm import tangent_norm          # noqa: E402,F401  (csrc/fc_norm.hip)
+from .dropout import philox_words, tangent_dropout          # noqa: E402,F401  (csrc/fc_dropout.hip, fc_philox.hpp)
+from .augment import mesh_affine, random_mesh_affine          # noqa: E402,F401  (csrc/fc_augment.hip)

@@ -18,8 +18,9 @@ from .tangent_norm import TangentNorm
 from .tangent_interpolate import TangentInterpolate
 from .tangent_max_pool import TangentMaxPool
 from .mesh_max_pool import MeshMaxPool
+from .tangent_dropout import TangentDropout
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
            'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval',
            'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'TangentNorm', 'TangentInterpolate',
-           'TangentMaxPool', 'MeshMaxPool', 'MeshPool']
+           'TangentMaxPool', 'MeshMaxPool', 'TangentDropout', 'MeshPool']

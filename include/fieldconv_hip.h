@@ -1015,6 +1015,63 @@ int fc_segment_max_forward(const void* x, const int64_t* ptr, int32_t N, int32_t
 int fc_segment_max_backward(const void* x, const void* grad_out, const int32_t* index, const int64_t* ptr, int32_t N, int32_t B, int32_t C,
                             int32_t dtype, int32_t is_complex, void* grad_x, void* stream);
 
+/* ---- a counter-based generator on the device, and dropout by a real mask (csrc/fc_philox.hpp, csrc/fc_dropout.hip) ------------- *
+ * generator  Philox4x32-10 as published (Salmon et al., SC'11; Random123): multipliers 0xD2511F53 and 0xCD9E8D57, key increments
+ *         0x9E3779B9 and 0xBB67AE85, ten rounds.  One round, from (c0, c1, c2, c3) and (k0, k1): p0 = M0 * c0 and p1 = M1 * c2 as
+ *         64-bit products, c = (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0)), then the key is bumped.
+ * draws   key = (lo32(seed), hi32(seed)); counter = (lo32(q), hi32(q), lo32(step), stream): q the 64-bit block number, step the
+ *         draw number (its low 32 bits), stream the user: 0 element dropout, 1 channel dropout, 2 augmentation.  Entry e of a draw
+ *         uses word e & 3 of block e >> 2; a uniform is u = (word >> 8) * 2^-24, exact in float32, in [0, 1).
+ * step    every entry point below that draws takes (step, step_ptr): with step_ptr NULL the draw number is step, else it is the
+ *         int64 step_ptr points to in DEVICE memory, read by the kernel when it runs -- no synchronisation, and the replay of a
+ *         captured launch sees the value of that time.
+ *
+ * fc_philox_words  the raw words, so that the generator itself can be pinned on the device: out (4 n_blocks) uint32, block i of it
+ *         the words of counter (lo32(q), hi32(q), lo32(hi), hi32(hi)), q = first_block + i (wrapping at 2^64), under the key of
+ *         seed.  n_blocks >= 0.
+ * fc_dropout  x, y (N, C) row-major, contiguous, dtype FC_F32 / FC_F64, is_complex 1 (interleaved pairs: complex64 / complex128) or
+ *         0; y must not be x.  threshold = floor(p * 2^24) for the drop probability p in [0, 1), computed by the CALLER in double;
+ *         scale = 1 / (1 - p) in double, rounded here once to dtype.  Entry e is dropped iff (word >> 8) < threshold, an integer
+ *         compare.  A kept entry is scale * x, one multiplication per scalar (re and im each) rounded on its own; a dropped entry
+ *         is +0 (+0 +0j) exactly, whatever x holds.  The mask is real: the whole complex entry is kept or dropped, which commutes
+ *         with any change of frames.
+ *           mode 0 (element, stream 0)  e = n C + c in 64-bit arithmetic; ptr and B are not read (B >= 1 all the same)
+ *           mode 1 (channel, stream 1)  e = b C + c, b the mesh of row n: mesh b owns the rows ptr[b] .. ptr[b+1] - 1 (ptr as in the
+ *                                       per-mesh pooling section: B+1 int64 in DEVICE memory, checked by the CALLER, clamped to
+ *                                       [0, N] by the kernel; NULL with B == 1: one mesh).  One decision per mesh and channel.
+ *         The gradient is the same call on grad_y: the mask is never stored.  A decision is a function of (seed, step, stream, e)
+ *         alone, so the result does not depend on the launch geometry.  x and y on 16-byte boundaries move 16 bytes per access in
+ *         mode 0, anything else one scalar; entries are aligned as in the max-pooling section (not checked).  N >= 0, B >= 1,
+ *         1 <= C <= 64 * 65535, N + 64 B < 2^31, threshold <= 2^24, scale > 0, else FC_ERR_BAD_ARGUMENT.
+ * One launch each, every output element written by one thread: no atomics, the same bits on every run.  No workspace, no
+ * allocation or synchronisation inside. */
+int fc_philox_words(uint64_t seed, uint64_t hi, uint64_t first_block, int64_t n_blocks, uint32_t* out, void* stream);
+int fc_dropout(const void* x, void* y, int32_t N, int32_t C, int32_t dtype, int32_t is_complex, int32_t mode, const int64_t* ptr, int32_t B,
+               uint32_t threshold, double scale, uint64_t seed, int64_t step, const int64_t* step_ptr, void* stream);
+
+/* ---- per-mesh augmentation: one random similarity per mesh of a batch (csrc/fc_augment.hip) ------------------------------------ *
+ * fc_mesh_affine_draw   params (B, 4) and M (B, 3, 3) float32, row-major.  Mesh b uses block q = b of stream 2 of the draw
+ *         (seed, step, step_ptr as above), u_k from word k:
+ *           s = scale_lo + (scale_hi - scale_lo) * u_0  (has_scale 1; with has_scale 0, s = 1 and u_0 is unused)
+ *           a_k = (2 * u_{k+1} - 1) * degrees_k, the angle about axis k in degrees;  params[b] = (s, a_0, a_1, a_2)
+ *         every operation a float32 operation rounded on its own, no fused multiply-add: numpy gives the same bits.  With
+ *         r_k = a_k * fl32(pi / 180), M[b] = s Rz(r_2) Ry(r_1) Rx(r_0), the right-handed rotations
+ *           Rx = [1 0 0; 0 c -s; 0 s c]   Ry = [c 0 s; 0 1 0; -s 0 c]   Rz = [c -s 0; s c 0; 0 0 1]
+ *         for column vectors: scale, then the rotation about axis 0, then 1, then 2.  sinf and cosf are the device library's, so M
+ *         is accurate to a few units in the last place and NOT bit-exact.  B >= 1.
+ * fc_mesh_affine_apply  pos (V, 3) float32; mesh b owns the vertices pos_ptr[b] .. pos_ptr[b+1] - 1 (B+1 int64, DEVICE memory,
+ *         checked by the caller, clamped to [0, V] by the kernel); M (B, 3, 3); t (B, 3) float32 or NULL; index (R) int64 or NULL
+ *         (then R output rows take the vertices 0 .. R - 1); out (R, 3).  Output row r takes vertex v = index[r] of the mesh b
+ *         that owns v:  d = p_v - t_b (p_v without t),  out_i = (M_i0 d_0 + M_i1 d_1) + M_i2 d_2, every operation rounded on
+ *         its own in float32.  A v outside [0, V) gives a row of NaN and reads nothing.  out must not overlap pos.
+ *         B >= 1, 0 <= V < 2^31, R >= 0.
+ * One launch each, one thread per mesh / per output row: no atomics, the same bits on every run.  No workspace, no allocation or
+ * synchronisation inside. */
+int fc_mesh_affine_draw(int32_t B, uint64_t seed, int64_t step, const int64_t* step_ptr, int32_t has_scale, float scale_lo, float scale_hi,
+                        float degrees0, float degrees1, float degrees2, float* params, float* M, void* stream);
+int fc_mesh_affine_apply(const float* pos, const int64_t* pos_ptr, int32_t B, int32_t V, const float* M, const float* t, const int64_t* index,
+                         int64_t R, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
