@@ -56,6 +56,18 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
 
 
+def by_value(t, align=0):
+    """The tensor a launch may take the pointer of in place of `t`: contiguous, lazy conjugate and negative bits resolved -- the kernels
+    read raw memory, and a bare .contiguous() hands a lazily conjugated or negated tensor back as it is.  A plain contiguous tensor is
+    returned ITSELF (no copy, no new tensor object); everything else is copied.  align: the bytes a kernel's vector loads assume of
+    the base address where that is more than the element size (a contiguous view may start anywhere in its storage): such a view is
+    copied too."""
+    t = t.resolve_conj().resolve_neg().contiguous()
+    if align and t.data_ptr() % align:
+        t = t.clone()
+    return t
+
+
 def scratch(nbytes, device, floor=0):
     """Device scratch of `nbytes` bytes (uint8), the ONE place workspaces are allocated.  What a zero-byte request gives follows the
     entry point: floor=0 an empty tensor (its pointer is NULL), floor=1 a live one-byte buffer (the block-level entry points),

@@ -137,8 +137,10 @@ class _ResnetBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, z1, s1, p1, b1, z2, s2, p2, b2, re_w, im_w, ftype, B, graph):
         lib = _lib.load()
-        x = x.contiguous()
-        tens = [t.contiguous() for t in (z1, s1, p1, b1, z2, s2, p2, b2, re_w, im_w)]
+        # (alignment: the spherical coefficients are read as float2 pairs -- csrc/fc_pack.hip, filter_entry -- and the residual mix takes
+        # its vector route on 16-byte aligned rows and 8-byte aligned filter rows only -- csrc/fc_pointwise.hip, lin_aligned)
+        x = Fn._by_value(x, 16)
+        tens = [Fn._by_value(t, a) for t, a in ((z1, 0), (s1, 8), (p1, 0), (b1, 0), (z2, 0), (s2, 8), (p2, 0), (b2, 0), (re_w, 8), (im_w, 8))]
         z1, s1, p1, b1, z2, s2, p2, b2, re_w, im_w = tens
         C_mid, C_in, C_out = z1.shape[0], z1.shape[1], z2.shape[0]
         mesh = _mesh(graph, B)
@@ -162,7 +164,7 @@ class _ResnetBlockFn(torch.autograd.Function):
         x, saved, z1, s1, p1, b1, z2, s2, p2, b2, re_w, im_w = ctx.saved_tensors
         graph, ftype, sizes = ctx.graph, ctx.ftype, ctx.sizes
         C_mid, C_in, C_out = z1.shape[0], z1.shape[1], z2.shape[0]
-        g_out = g_out.contiguous()
+        g_out = Fn._by_value(g_out)
         mesh = _mesh(graph, ctx.B)
         dev = x.device
         has_phase = ftype == 1
@@ -234,8 +236,8 @@ class _EchoBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, zonal, spherical, phase, bias, ftype, B, n_des, n_bins, graph, slots):
         lib = _lib.load()
-        x = x.contiguous()
-        zonal, spherical, phase, bias = zonal.contiguous(), spherical.contiguous(), phase.contiguous(), bias.contiguous()
+        x = Fn._by_value(x)
+        zonal, spherical, phase, bias = Fn._by_value(zonal), Fn._by_value(spherical, 8), Fn._by_value(phase), Fn._by_value(bias)
         C_in = zonal.shape[1]
         mesh = _mesh(graph, B)
         bp = FcEchoBlockParams(C_in, n_des, n_bins, Fn._filter_params((zonal, spherical, phase, ftype)), bias.data_ptr(), None)
@@ -256,7 +258,7 @@ class _EchoBlockFn(torch.autograd.Function):
         lib = _lib.load()
         x, saved, zonal, spherical, phase, bias = ctx.saved_tensors
         graph, ftype, sizes, slots = ctx.graph, ctx.ftype, ctx.sizes, ctx.slots
-        g_desc = g_desc.contiguous()
+        g_desc = Fn._by_value(g_desc)
         mesh = _mesh(graph, ctx.B)
         dev = x.device
         shapes = [zonal.shape, spherical.shape, phase.shape if ftype == 1 else None, bias.shape]
@@ -302,7 +304,8 @@ class _EchoTailFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, d, x, w1, b1, w2, b2, w3, b3, wr, br):
         lib = _lib.load()
-        x = x.contiguous()
+        x = Fn._by_value(x)
+        w1, b1, w2, b2, w3, b3, wr, br = (Fn._by_value(t) for t in (w1, b1, w2, b2, w3, b3, wr, br))          # (one GEMM layout, whatever view)
         with Fn._on(x.device):
             a = torch.empty(x.shape, dtype=torch.float32, device=x.device)
             check(lib.fc_soft_abs_forward(Fn._p(x), Fn._p(a), x.numel(), Fn._stream()), 'fc_soft_abs_forward')
@@ -316,7 +319,7 @@ class _EchoTailFn(torch.autograd.Function):
     def backward(ctx, g):
         lib = _lib.load()
         d, x, a, h1, h2, w1, w2, w3, wr = ctx.saved_tensors
-        g = g.contiguous()
+        g = Fn._by_value(g)
         with Fn._on(x.device):
             gb = g.sum(0)                                   # lin3.bias and res.bias see the same cotangent
             g_w3 = g.t().mm(h2)
@@ -352,7 +355,8 @@ class _EchoHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, d, x, w1, b1, w2, b2, w3, b3, wr, br):
         lib = _lib.load()
-        d, x = d.contiguous(), x.contiguous()
+        d, x = Fn._by_value(d), Fn._by_value(x)
+        w1, b1, w2, b2, w3, b3, wr, br = (Fn._by_value(t) for t in (w1, b1, w2, b2, w3, b3, wr, br))
         N = int(d.shape[0])
         D, H1, H2, C, Q = _head_params(d, x, w1, w2, w3, wr)
         hp = _lib.FcEchoHeadParams(D, H1, H2, C, Q, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(),
@@ -371,7 +375,7 @@ class _EchoHeadFn(torch.autograd.Function):
     def backward(ctx, g):
         lib = _lib.load()
         d, x, h1, h2, w1, w2, w3, wr = ctx.saved_tensors
-        g = g.contiguous()
+        g = Fn._by_value(g)
         N = int(d.shape[0])
         D, H1, H2, C, Q = _head_params(d, x, w1, w2, w3, wr)
         with Fn._on(x.device):
@@ -400,7 +404,7 @@ def echo_block_tail(block, d, x):
     tens = []
     for lin in layers:
         w, b = lin._parameters.get('weight'), lin._parameters.get('bias')
-        if type(lin) is not torch.nn.Linear or w is None or b is None or w.dtype != torch.float32 or not w.is_contiguous():
+        if type(lin) is not torch.nn.Linear or w is None or b is None or w.dtype != torch.float32:          # (views: the nodes take them by value)
             return None
         tens += [w, b]
     # FIELDCONV_ECHO_TAIL=aten (development): the tail composed of ATen GEMMs inside one node, as before the native head
@@ -418,8 +422,8 @@ class _LiftBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sten, stride, zonal_ang, zonal_mag, phase, bias, ftype, csr):
         lib = _lib.load()
-        x = x.contiguous()
-        zonal_ang, zonal_mag, phase, bias = zonal_ang.contiguous(), zonal_mag.contiguous(), phase.contiguous(), bias.contiguous()
+        x = Fn._by_value(x)
+        zonal_ang, zonal_mag, phase, bias = Fn._by_value(zonal_ang), Fn._by_value(zonal_mag), Fn._by_value(phase), Fn._by_value(bias)
         N, C_in = x.shape
         C_out, _, R = zonal_ang.shape
         by_t, by_s = Fn._by_target(csr), Fn._by_source(csr)
@@ -443,7 +447,7 @@ class _LiftBlockFn(torch.autograd.Function):
         sten, saved, zonal_ang, zonal_mag, phase, bias = ctx.saved_tensors
         csr, ftype = ctx.csr, ctx.ftype
         N, C_in, C_out, R = ctx.dims
-        g_out = g_out.contiguous()
+        g_out = Fn._by_value(g_out)
         by_t, by_s = Fn._by_target(csr), Fn._by_source(csr)
         mesh = FcMesh(N, csr.E, R, 0, 0, ctypes.pointer(by_t), ctypes.pointer(by_s), None, None)
         dev = g_out.device

@@ -69,6 +69,16 @@ void* stream_of(const at::Tensor& t) { return c10::hip::getCurrentHIPStream(t.de
 const float* fp(const at::Tensor& t) { return t.defined() && t.numel() ? static_cast<const float*>(t.data_ptr()) : nullptr; }
 float* fpm(const at::Tensor& t) { return t.defined() && t.numel() ? static_cast<float*>(t.data_ptr()) : nullptr; }
 
+// The tensor a launch may take the pointer of in place of `t` (fieldconv_amd/_launch.py: by_value): contiguous, lazy conjugate and negative
+// bits resolved -- a bare contiguous() hands a lazily conjugated or negated tensor back as it is.  A plain contiguous tensor is returned
+// itself, without a copy.  align: the bytes a kernel's vector loads assume of the base address where that is more than the element size
+// (the spherical coefficients are read as float2 pairs, the residual mix takes its vector route on 16-byte rows only).
+at::Tensor by_value(const at::Tensor& t, int64_t align = 0) {
+    at::Tensor r = t.resolve_conj().resolve_neg().contiguous();
+    if (align && r.numel() && reinterpret_cast<uintptr_t>(r.data_ptr()) % (uintptr_t)align) r = r.clone();
+    return r;
+}
+
 // One mesh's support graph as the block-level calls take it: the grouping arrays and records (kept alive here), sizes, record kind.
 // Built once per (graph, band limit) by the Python side and handed to every node of that mesh.
 struct GraphRef {
@@ -139,9 +149,9 @@ struct ResnetBlockFn : public torch::autograd::Function<ResnetBlockFn> {
                               const at::Tensor& b1_, const at::Tensor& z2_, const at::Tensor& s2_, const at::Tensor& p2_, const at::Tensor& b2_,
                               const at::Tensor& re_, const at::Tensor& im_, const std::shared_ptr<GraphRef>& g, int64_t ftype,
                               int64_t saved_bytes, int64_t ws_fwd, int64_t ws_bwd) {
-        const at::Tensor x = x_.contiguous(), z1 = z1_.contiguous(), s1 = s1_.contiguous(), p1 = p1_.contiguous(), b1 = b1_.contiguous(),
-                         z2 = z2_.contiguous(), s2 = s2_.contiguous(), p2 = p2_.contiguous(), b2 = b2_.contiguous(), re = re_.contiguous(),
-                         im = im_.contiguous();
+        const at::Tensor x = by_value(x_, 16), z1 = by_value(z1_), s1 = by_value(s1_, 8), p1 = by_value(p1_), b1 = by_value(b1_),
+                         z2 = by_value(z2_), s2 = by_value(s2_, 8), p2 = by_value(p2_), b2 = by_value(b2_), re = by_value(re_, 8),
+                         im = by_value(im_, 8);
         c10::DeviceGuard guard(x.device());
         fc_mesh m;
         fc_csr ct, cs;
@@ -176,7 +186,7 @@ struct ResnetBlockFn : public torch::autograd::Function<ResnetBlockFn> {
                       ws_bwd = ctx->saved_data["ws_bwd"].toInt();
         const GraphRef gr = load_graph(ctx);
         const GraphRef* g = &gr;
-        const at::Tensor g_out = grads[0].contiguous();
+        const at::Tensor g_out = by_value(grads[0]);
         c10::DeviceGuard guard(x.device());
         fc_mesh m;
         fc_csr ct, cs;
@@ -213,7 +223,7 @@ struct EchoBlockFn : public torch::autograd::Function<EchoBlockFn> {
     static at::Tensor forward(AutogradContext* ctx, const at::Tensor& x_, const at::Tensor& z_, const at::Tensor& s_, const at::Tensor& p_,
                               const at::Tensor& bias_, const std::shared_ptr<GraphRef>& g, const std::vector<at::Tensor>& slots, int64_t ftype,
                               int64_t n_des, int64_t n_bins, int64_t dS, int64_t saved_bytes, int64_t ws_fwd, int64_t ws_bwd) {
-        const at::Tensor x = x_.contiguous(), z = z_.contiguous(), s = s_.contiguous(), p = p_.contiguous(), bias = bias_.contiguous();
+        const at::Tensor x = by_value(x_), z = by_value(z_), s = by_value(s_, 8), p = by_value(p_), bias = by_value(bias_);
         TORCH_CHECK(slots.size() == 4, "EchoBlockFn takes ln_t, wxp_t, ln_s, wxp_s");
         c10::DeviceGuard guard(x.device());
         fc_mesh m;
@@ -242,7 +252,7 @@ struct EchoBlockFn : public torch::autograd::Function<EchoBlockFn> {
         const auto ints = ctx->saved_data["ints"].toIntVector();
         const int64_t ftype = ints[0], n_des = ints[1], n_bins = ints[2], saved_bytes = ints[3], ws_bwd = ints[4];
         const GraphRef g = load_graph(ctx);
-        const at::Tensor g_desc = grads[0].contiguous();
+        const at::Tensor g_desc = by_value(grads[0]);
         c10::DeviceGuard guard(x.device());
         fc_mesh m;
         fc_csr ct, cs;
@@ -281,7 +291,7 @@ struct LiftBlockFn : public torch::autograd::Function<LiftBlockFn> {
     static at::Tensor forward(AutogradContext* ctx, const at::Tensor& x_, const at::Tensor& sten, const at::Tensor& za_, const at::Tensor& zm_,
                               const at::Tensor& ph_, const at::Tensor& bias_, const std::vector<at::Tensor>& csr, int64_t stride, int64_t ftype,
                               int64_t E) {
-        const at::Tensor x = x_.contiguous(), za = za_.contiguous(), zm = zm_.contiguous(), ph = ph_.contiguous(), bias = bias_.contiguous();
+        const at::Tensor x = by_value(x_), za = by_value(za_), zm = by_value(zm_), ph = by_value(ph_), bias = by_value(bias_);
         TORCH_CHECK(csr.size() == 6, "LiftBlockFn takes rowptr_t, nbr_t, perm_t, rowptr_s, nbr_s, perm_s");
         const int64_t N = x.size(0), C_in = x.size(1), C_out = za.size(0), R = za.size(2);
         c10::DeviceGuard guard(x.device());
@@ -312,7 +322,7 @@ struct LiftBlockFn : public torch::autograd::Function<LiftBlockFn> {
         const at::Tensor &sten = sv[0], &saved = sv[1], &za = sv[2], &zm = sv[3], &ph = sv[4], &bias = sv[5];
         const auto ints = ctx->saved_data["ints"].toIntVector();
         const int64_t N = ints[0], C_in = ints[1], stride = ints[2], ftype = ints[3], E = ints[4], saved_bytes = ints[5];
-        const at::Tensor g_out = grads[0].contiguous();
+        const at::Tensor g_out = by_value(grads[0]);
         c10::DeviceGuard guard(g_out.device());
         fc_mesh m;
         fc_csr ct, cs;
@@ -344,10 +354,11 @@ struct LiftBlockFn : public torch::autograd::Function<LiftBlockFn> {
 // lin3(relu(lin2(relu(lin1(d))))) + res(softAbs(x)), reference nn/echo_block.py:95-103: the reference's four dense layers (ATen GEMMs, i.e.
 // hipBLASLt) and softAbs (fc_soft_abs_*) as ONE node with the backward pass written out
 struct EchoTailFn : public torch::autograd::Function<EchoTailFn> {
-    static at::Tensor forward(AutogradContext* ctx, const at::Tensor& d, const at::Tensor& x_, const at::Tensor& w1, const at::Tensor& b1,
-                              const at::Tensor& w2, const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3, const at::Tensor& wr,
-                              const at::Tensor& br) {
-        const at::Tensor x = x_.contiguous();
+    static at::Tensor forward(AutogradContext* ctx, const at::Tensor& d, const at::Tensor& x_, const at::Tensor& w1_, const at::Tensor& b1_,
+                              const at::Tensor& w2_, const at::Tensor& b2_, const at::Tensor& w3_, const at::Tensor& b3_, const at::Tensor& wr_,
+                              const at::Tensor& br_) {
+        const at::Tensor x = by_value(x_), w1 = by_value(w1_), b1 = by_value(b1_), w2 = by_value(w2_), b2 = by_value(b2_), w3 = by_value(w3_),
+                         b3 = by_value(b3_), wr = by_value(wr_), br = by_value(br_);          // (one GEMM layout, whatever view)
         c10::DeviceGuard guard(x.device());
         at::Tensor a = at::empty(x.sizes(), x.options().dtype(at::kFloat));
         check(api.soft_abs_fwd(fp(x), fpm(a), (size_t)x.numel(), stream_of(x)), "fc_soft_abs_forward");
@@ -361,7 +372,7 @@ struct EchoTailFn : public torch::autograd::Function<EchoTailFn> {
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
         const auto sv = ctx->get_saved_variables();
         const at::Tensor &d = sv[0], &x = sv[1], &a = sv[2], &h1 = sv[3], &h2 = sv[4], &w1 = sv[5], &w2 = sv[6], &w3 = sv[7], &wr = sv[8];
-        const at::Tensor g = grads[0].contiguous();
+        const at::Tensor g = by_value(grads[0]);
         c10::DeviceGuard guard(x.device());
         at::Tensor gb = g.sum(0);                            // lin3.bias and res.bias see the same cotangent
         at::Tensor g_w3 = g.t().mm(h2);
@@ -393,10 +404,11 @@ struct EchoHeadFn : public torch::autograd::Function<EchoHeadFn> {
         p.w1 = fp(w1); p.w2 = fp(w2); p.w3 = fp(w3); p.wr = fp(wr);
         return p;
     }
-    static at::Tensor forward(AutogradContext* ctx, const at::Tensor& d_, const at::Tensor& x_, const at::Tensor& w1, const at::Tensor& b1,
-                              const at::Tensor& w2, const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3, const at::Tensor& wr,
-                              const at::Tensor& br) {
-        const at::Tensor d = d_.contiguous(), x = x_.contiguous();
+    static at::Tensor forward(AutogradContext* ctx, const at::Tensor& d_, const at::Tensor& x_, const at::Tensor& w1_, const at::Tensor& b1_,
+                              const at::Tensor& w2_, const at::Tensor& b2_, const at::Tensor& w3_, const at::Tensor& b3_, const at::Tensor& wr_,
+                              const at::Tensor& br_) {
+        const at::Tensor d = by_value(d_), x = by_value(x_), w1 = by_value(w1_), b1 = by_value(b1_), w2 = by_value(w2_), b2 = by_value(b2_),
+                         w3 = by_value(w3_), b3 = by_value(b3_), wr = by_value(wr_), br = by_value(br_);
         c10::DeviceGuard guard(x.device());
         fc_echo_head_params p = params(d, x, w1, w2, w3, wr);
         p.b1 = fp(b1); p.b2 = fp(b2); p.b3 = fp(b3); p.br = fp(br);
@@ -415,7 +427,7 @@ struct EchoHeadFn : public torch::autograd::Function<EchoHeadFn> {
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
         const auto sv = ctx->get_saved_variables();
         const at::Tensor &d = sv[0], &x = sv[1], &h1 = sv[2], &h2 = sv[3], &w1 = sv[4], &w2 = sv[5], &w3 = sv[6], &wr = sv[7];
-        const at::Tensor g = grads[0].contiguous();
+        const at::Tensor g = by_value(grads[0]);
         c10::DeviceGuard guard(x.device());
         fc_echo_head_params p = params(d, x, w1, w2, w3, wr);
         const int64_t N = d.size(0);

@@ -20,7 +20,7 @@ Features are (N,C) tensors on a ROCm device; there is no CPU or eager path: a CP
 import torch
 
 from . import _lib
-from ._launch import on as _on, ptr as _ptr, stream as _stream, whole as _whole
+from ._launch import by_value as _by_value, on as _on, ptr as _ptr, stream as _stream, whole as _whole
 from .pooling import check_ptr, ptr_on
 
 _DTYPES = {torch.float32: (0, 0), torch.float64: (1, 0), torch.complex64: (0, 1), torch.complex128: (1, 1)}          # (fc_dtype, is_complex)
@@ -80,7 +80,7 @@ def _launch(x, ptr, B, threshold, scale, seed, step, step_t, mode):
 class _TangentDropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ptr, B, threshold, scale, seed, step, step_t, mode):
-        xc = x.detach().resolve_conj().resolve_neg().contiguous()
+        xc = _by_value(x.detach())
         # the step the backward pass draws with: the int, or the device tensor's value of NOW (its owner advances it after the
         # call), cloned before the launch -- only when there will be a backward pass
         need = ctx.needs_input_grad[0]
@@ -95,7 +95,7 @@ class _TangentDropout(torch.autograd.Function):
             return (None,) * 9
         ptr, kept = ctx.saved_tensors
         B, threshold, scale, seed, step, mode, xdt = ctx.meta
-        gy = gy.detach().to(xdt).resolve_conj().resolve_neg().contiguous()
+        gy = _by_value(gy.detach().to(xdt))
         return (_launch(gy, ptr, B, threshold, scale, seed, step, kept, mode),) + (None,) * 8
 
 

@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib
-from ._launch import NO_GUARD as _NO_GUARD, _dp, _p, _po, carve as _carve, on as _on, scratch as _scratch, stream as _stream          # noqa: F401  (blocks.py and the tests reach them as Fn._*)
+from ._launch import NO_GUARD as _NO_GUARD, _dp, _p, _po, by_value as _by_value, carve as _carve, on as _on, scratch as _scratch, stream as _stream          # noqa: F401  (blocks.py and the tests reach them as Fn._*)
 from ._lib import FcCsr, FcDims, FcEpilogue, FcFilterParams, check
 
 
@@ -146,8 +146,8 @@ class _FieldConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_eff, graph):
         lib = _lib.load()
-        x = x.contiguous()
-        w_eff = w_eff.contiguous()
+        x = _by_value(x)
+        w_eff = _by_value(w_eff)
         O, I, R, F = w_eff.shape
         B = (F - 1) // 2
         plan = _conv_plan(lib, graph, I, O, B)
@@ -168,7 +168,7 @@ class _FieldConvFn(torch.autograd.Function):
         x, wpk_b = ctx.saved_tensors
         O, I, R, F = ctx.wshape
         plan = _conv_plan(lib, ctx.graph, I, O, (F - 1) // 2)
-        gy = gy.contiguous()
+        gy = _by_value(gy)
         with _on(x.device):
             gx, gw, _ = _launch_backward(lib, x, gy, ctx.graph, wpk_b, plan, ctx.wshape, _stream())
         return gx, gw, None
@@ -383,8 +383,8 @@ class _FieldConvParamFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, zonal, spherical, phase, ftype, B, graph):
         lib = _lib.load()
-        x = x.contiguous()
-        zonal, spherical, phase = zonal.contiguous(), spherical.contiguous(), phase.contiguous()
+        x = _by_value(x)
+        zonal, spherical, phase = _by_value(zonal), _by_value(spherical, 8), _by_value(phase)
         O, I, R = zonal.shape[0], zonal.shape[1], zonal.shape[2]
         F = 2 * B + 1
         plan = _conv_plan(lib, graph, I, O, B)
@@ -402,7 +402,7 @@ class _FieldConvParamFn(torch.autograd.Function):
         x, wpk_b, zonal, spherical, phase = ctx.saved_tensors
         O, I, R, F = ctx.wshape
         plan = _conv_plan(lib, ctx.graph, I, O, (F - 1) // 2)
-        gy = gy.contiguous()
+        gy = _by_value(gy)
         with _on(x.device):
             st = _stream()
             gx, _, (g_z, g_s, g_p) = _launch_backward(lib, x, gy, ctx.graph, wpk_b, plan, ctx.wshape, st,
@@ -419,10 +419,10 @@ class _FieldConvActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, zonal, spherical, phase, bias, addend, ftype, B, graph):
         lib = _lib.load()
-        x = x.contiguous()
-        zonal, spherical, phase = zonal.contiguous(), spherical.contiguous(), phase.contiguous()
-        bias = bias.contiguous()
-        addend = addend.contiguous() if addend is not None else None
+        x = _by_value(x)
+        zonal, spherical, phase = _by_value(zonal), _by_value(spherical, 8), _by_value(phase)
+        bias = _by_value(bias)
+        addend = _by_value(addend) if addend is not None else None
         O, I, R = zonal.shape[0], zonal.shape[1], zonal.shape[2]
         F = 2 * B + 1
         plan = _conv_plan(lib, graph, I, O, B)
@@ -440,7 +440,7 @@ class _FieldConvActFn(torch.autograd.Function):
         x, wpk_b, zonal, spherical, phase, bias, pre = ctx.saved_tensors
         O, I, R, F = ctx.wshape
         plan = _conv_plan(lib, ctx.graph, I, O, (F - 1) // 2)
-        g_act = g_act.contiguous()
+        g_act = _by_value(g_act)
         N = pre.shape[0]
         with _on(x.device):
             st = _stream()
@@ -504,7 +504,7 @@ class _GenericFieldConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_eff, graph):
         lib = _lib.load()
-        x = x.contiguous()
+        x, w_eff = _by_value(x), _by_value(w_eff)
         O, I, R, F = w_eff.shape
         B = (F - 1) // 2
         nt, K = graph.n_targets, I * R * F
@@ -532,7 +532,7 @@ class _GenericFieldConvFn(torch.autograd.Function):
         O, I, R, F = w_eff.shape
         B = (F - 1) // 2
         nt, K = graph.n_targets, I * R * F
-        gy = gy.contiguous()
+        gy = _by_value(gy)
         with _on(x.device):
             contrib = _GenericFieldConvFn._gather(lib, x, graph, I, R, B)      # recomputed, not kept between the passes
             g_contrib = torch.empty((nt, K), dtype=x.dtype, device=x.device)
@@ -552,7 +552,7 @@ def _generic_field_conv(x, w_eff, graph):
                                             'float32 data: records only)')
         raise _lib.FieldConvNativeError('the run-time FieldConv path needs a support graph with dense stencil rows')
     _check_conv(x, graph, *w_eff.shape[1:], dtypes=(torch.complex64, torch.complex128), same=(w_eff, graph.sten_t))
-    return _GenericFieldConvFn.apply(x, w_eff.contiguous(), graph)
+    return _GenericFieldConvFn.apply(x, w_eff, graph)
 
 
 def _run_time_path(x, graph):
@@ -577,13 +577,13 @@ class _WideFieldConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, zonal, spherical, phase, w_eff, ftype, B, graph, blk):
         lib = _lib.load()
-        x = x.contiguous()
+        x = _by_value(x)
         explicit = w_eff is not None
         if explicit:
-            w_eff = w_eff.contiguous()
+            w_eff = _by_value(w_eff)
             O, I = w_eff.shape[0], w_eff.shape[1]
         else:
-            zonal, spherical, phase = zonal.contiguous(), spherical.contiguous(), phase.contiguous()
+            zonal, spherical, phase = _by_value(zonal), _by_value(spherical, 8), _by_value(phase)
             O, I = zonal.shape[0], zonal.shape[1]
         dims = make_dims(graph, I, O, B)
         records = 1 if graph.factored else 0
@@ -607,7 +607,7 @@ class _WideFieldConvFn(torch.autograd.Function):
         graph, blk = ctx.graph, ctx.blk
         I, O = ctx.io
         x = ctx.saved_tensors[0]
-        gy = gy.contiguous()
+        gy = _by_value(gy)
         dims = make_dims(graph, I, O, ctx.B)
         records = 1 if graph.factored else 0
         sten = _records(graph)[2]
@@ -700,9 +700,11 @@ class _TangentLinFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, re_w, im_w):
         lib = _lib.load()
-        x = x.contiguous()
-        re_w = re_w.contiguous()
-        im_w = im_w.contiguous()
+        # (the kernels take their float4 / float2 route only on 16-byte aligned rows and 8-byte aligned filter rows: csrc/fc_pointwise.hip,
+        # lin_aligned; an offset view is copied, so the route -- and the bits of the result -- do not follow where a view starts)
+        x = _by_value(x, 16)
+        re_w = _by_value(re_w, 8)
+        im_w = _by_value(im_w, 8)
         O, I = re_w.shape
         N = x.shape[0]
         with _on(x.device):
@@ -717,7 +719,7 @@ class _TangentLinFn(torch.autograd.Function):
         x, re_w, im_w = ctx.saved_tensors
         O, I = re_w.shape
         N = x.shape[0]
-        gy = gy.contiguous()
+        gy = _by_value(gy, 16)
         with _on(x.device):
             gx = torch.empty_like(x)
             g_re = torch.empty_like(re_w)
@@ -736,7 +738,7 @@ class _TangentLinGemmFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, re_w, im_w):
         lib = _lib.load()
-        x = x.contiguous()
+        x = _by_value(x)
         wc = torch.complex(re_w, im_w).contiguous()
         O, I = wc.shape
         N = x.shape[0]
@@ -752,7 +754,7 @@ class _TangentLinGemmFn(torch.autograd.Function):
         x, wc = ctx.saved_tensors
         O, I = wc.shape
         N = x.shape[0]
-        gy = gy.contiguous()
+        gy = _by_value(gy)
         with _on(x.device):
             gx = torch.empty_like(x)
             _cgemm(lib, gy, wc, gx, N, I, O, O, 1, I, 1, True, 1.0)                       # gy . conj(Wc)
@@ -780,8 +782,8 @@ def tangent_lin(x, re_w, im_w):
 def _nonlin_forward(ctx, x, bias, sfx):
     """modReLU forward; sfx '' (float32, csrc/fc_pointwise.hip) or '_f64' (csrc/fc_pointwise_f64.hip) picks the entry points"""
     lib = _lib.load()
-    x = x.contiguous()
-    b = bias.contiguous()
+    x = _by_value(x)
+    b = _by_value(bias)
     N, C = x.shape
     name = 'fc_tangent_nonlin_forward' + sfx
     with _on(x.device):
@@ -795,7 +797,7 @@ def _nonlin_backward(ctx, gy, sfx):
     lib = _lib.load()
     x, b = ctx.saved_tensors
     N, C = x.shape
-    gy = gy.contiguous()
+    gy = _by_value(gy)
     name = 'fc_tangent_nonlin_backward' + sfx
     with _on(x.device):
         gx = torch.empty_like(x)
@@ -849,7 +851,7 @@ class _SoftAbsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         lib = _lib.load()
-        x = x.contiguous()
+        x = _by_value(x)
         with _on(x.device):
             y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
             check(lib.fc_soft_abs_forward(_p(x), _p(y), x.numel(), _stream()), 'fc_soft_abs_forward')
@@ -860,7 +862,7 @@ class _SoftAbsFn(torch.autograd.Function):
     def backward(ctx, gy):
         lib = _lib.load()
         x, = ctx.saved_tensors
-        gy = gy.contiguous()
+        gy = _by_value(gy)
         with _on(x.device):
             gx = torch.empty_like(x)
             check(lib.fc_soft_abs_backward(_p(x), _p(gy), _p(gx), x.numel(), _stream()), 'fc_soft_abs_backward')
@@ -909,7 +911,7 @@ class _EchoFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, slots, csr, n_bins):
         lib = _lib.load()
-        x = x.contiguous()
+        x = _by_value(x)
         N, C = x.shape
         dS = lib.fc_echo_hist_dim(n_bins)
         with _on(x.device):
@@ -926,7 +928,7 @@ class _EchoFn(torch.autograd.Function):
         x, hist = ctx.saved_tensors
         csr, slots = ctx.csr, ctx.slots
         N, C = x.shape
-        g_desc = g_desc.contiguous()
+        g_desc = _by_value(g_desc)
         with _on(x.device):
             gx = torch.empty_like(x)
             gh = torch.empty_like(hist)
@@ -942,7 +944,7 @@ class _EchoGenericFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, slots, csr, n_bins):
         lib = _lib.load()
-        x = x.contiguous()
+        x = _by_value(x)
         N, C = x.shape
         dS = lib.fc_echo_hist_dim_generic(n_bins)
         if dS == 0:
@@ -964,7 +966,7 @@ class _EchoGenericFn(torch.autograd.Function):
         x, hist = ctx.saved_tensors
         csr, slots = ctx.csr, ctx.slots
         N, C = x.shape
-        g_desc = g_desc.contiguous()
+        g_desc = _by_value(g_desc)
         with _on(x.device):
             gx = torch.empty_like(x)
             gh = torch.empty_like(hist)
@@ -1016,23 +1018,24 @@ class _TransFieldFn(torch.autograd.Function):
         from .graph import LiftColumns
         if isinstance(lift_sten, LiftColumns):
             if lift_sten._dense is None:
-                return lift_sten.factors, 0
+                return _by_value(lift_sten.factors, 16), 0          # (read as two float4 per edge: csrc/fc_trans_field.hip, tf_load_sten)
             lift_sten = lift_sten._dense
+        lift_sten = lift_sten.resolve_conj().resolve_neg()          # (a view stays a view: its strides are looked at next)
         # (E,R,2) view of the full stencil (supp_sten[..., B:B+2], reference segmentation.ipynb:204) is read in place
         E, R, two = lift_sten.shape
         st = lift_sten.stride()
         if two == 2 and st[2] == 1 and st[0] == R * st[1] and st[1] >= 2:
             return lift_sten, int(st[1])
-        return lift_sten.contiguous(), 2
+        return _by_value(lift_sten), 2
 
     @staticmethod
     def forward(ctx, x, sten, stride, zonal_ang, zonal_mag, phase, csr, ftype):
         # (sten, stride) = _TransFieldFn._stencil(lift_sten), resolved by the caller
         lib = _lib.load()
-        x = x.contiguous()
+        x = _by_value(x)
         N, Cin = x.shape
         O, _, R = zonal_ang.shape
-        zonal_ang, zonal_mag, phase = zonal_ang.contiguous(), zonal_mag.contiguous(), phase.contiguous()
+        zonal_ang, zonal_mag, phase = _by_value(zonal_ang), _by_value(zonal_mag), _by_value(phase)
         with _on(x.device):
             y, ang, mag, s1sum = _trans_field_outputs(x, O, R)
             check(lib.fc_trans_field_forward(_p(x), _p(sten), ctypes.byref(_by_target(csr)), _p(csr.perm_t), _p(zonal_ang), _p(zonal_mag),
@@ -1049,7 +1052,7 @@ class _TransFieldFn(torch.autograd.Function):
         csr, Cin = ctx.csr, ctx.Cin
         O, _, R = zonal_ang.shape
         N = ang.shape[0]
-        gy = gy.contiguous()
+        gy = _by_value(gy)
         with _on(gy.device):
             gx, g_za, g_zm, g_ph = _trans_field_grads(mag, Cin, zonal_ang, zonal_mag, phase, ctx.ftype)
             nbytes = lib.fc_trans_field_backward_workspace_bytes(N, Cin, O, R)
@@ -1069,12 +1072,12 @@ class _TransFieldGenericFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sten, zonal_ang, zonal_mag, phase, csr, ftype):
         lib = _lib.load()
-        x = x.contiguous()
-        sten = sten.contiguous()                      # (E, R, >= 2) complex, the x's precision
+        x = _by_value(x)
+        sten = _by_value(sten)                      # (E, R, >= 2) complex, the x's precision
         N, Cin = x.shape
         O, _, R = zonal_ang.shape
         stride = int(sten.shape[2])
-        zonal_ang, zonal_mag, phase = zonal_ang.contiguous(), zonal_mag.contiguous(), phase.contiguous()
+        zonal_ang, zonal_mag, phase = _by_value(zonal_ang), _by_value(zonal_mag), _by_value(phase)
         dt = _dtype_code(x)
         with _on(x.device):
             y, ang, mag, s1sum = _trans_field_outputs(x, O, R)
@@ -1092,7 +1095,7 @@ class _TransFieldGenericFn(torch.autograd.Function):
         csr, Cin = ctx.csr, ctx.Cin
         O, _, R = zonal_ang.shape
         N = ang.shape[0]
-        gy = gy.contiguous()
+        gy = _by_value(gy)
         with _on(gy.device):
             gx, g_za, g_zm, g_ph = _trans_field_grads(mag, Cin, zonal_ang, zonal_mag, phase, ctx.ftype)
             nbytes = lib.fc_trans_field_backward_generic_workspace_bytes(N, Cin, O, R, ctx.dt)

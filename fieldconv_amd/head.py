@@ -9,7 +9,7 @@ float32 only, contiguous tensors only; there is no CPU or eager path: a CPU tens
 import torch
 
 from . import _lib
-from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
+from ._launch import by_value as _by_value, on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
 from .matching import MAX_K
 
 MAX_PARTS = 64
@@ -36,6 +36,8 @@ def _head_inputs(h, weight, bias, what, smoothed=False):
     for name, x, dim, shape in ops:
         if not x.is_contiguous():
             raise ValueError(f'{what}: {name} is not contiguous (call .contiguous() on it: the head copies nothing)')
+        if x.is_neg():          # (float32 operands: no conjugate bit; memory under a lazy negative holds the opposite numbers)
+            raise ValueError(f'{what}: {name} is a lazy negative (call .resolve_neg() on it: the head copies nothing)')
     for name, x, dim, shape in ops:
         if not x.is_cuda:
             raise RuntimeError(f'{what}: {name} is on {x.device}; the fused head runs on a ROCm device and has no CPU path')
@@ -91,9 +93,9 @@ class _LinearCrossEntropy(torch.autograd.Function):
         with _on(dev):
             g = g.detach().to(torch.float32)
             if reduction == 'none':
-                scale = g.contiguous()
+                scale = _by_value(g)
             else:          # the per-row upstream scale: g, or g / (rows that count)
-                scale = (g if reduction == 'sum' else g / total[2]).reshape(1).expand(N).contiguous()
+                scale = _by_value((g if reduction == 'sum' else g / total[2]).reshape(1).expand(N))
             if need_h:
                 g_h = torch.empty((N, H), dtype=torch.float32, device=dev)
                 _lib.check(lib.fc_linear_ce_backward_input(_ptr(h), _ptr(weight), _ptr(bias), _ptr(target), _ptr(lse), _ptr(scale), N, H, K,

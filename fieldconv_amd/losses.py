@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
+from ._launch import by_value as _by_value, on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
 
 _DTYPES = {torch.float32: 0, torch.float64: 1}
 MAX_THRESHOLDS = 16
@@ -65,7 +65,7 @@ def pair_sqdist(xS, xT, pairs):
     pairs = _pairs(pairs, xS.device, 'pair_sqdist', 'pairs')
     if bool(_bad_pairs(pairs, xT.shape[0], xS.shape[0])):
         raise IndexError(f'pair_sqdist: pair index outside xT ({xT.shape[0]} rows) x xS ({xS.shape[0]} rows)')
-    return _sqdist_unchecked(xS.detach().contiguous(), xT.detach().contiguous(), pairs)
+    return _sqdist_unchecked(_by_value(xS.detach()), _by_value(xT.detach()), pairs)
 
 
 def _row_segments(rows, n):
@@ -79,7 +79,7 @@ class _TwinLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xS, xT, p_, n_, yN, mu):
         lib = _lib.load()
-        xSc, xTc = xS.detach().contiguous(), xT.detach().contiguous()
+        xSc, xTc = _by_value(xS.detach()), _by_value(xT.detach())
         P, M = int(p_.shape[0]), int(n_.shape[0])
         dev, dt = xS.device, xS.dtype
         with _on(dev):
@@ -105,7 +105,7 @@ class _TwinLoss(torch.autograd.Function):
             rows = torch.cat((p_, n_), 0)
             rowptr_T, order_T = _row_segments(rows[:, 0].contiguous(), xT.shape[0])
             rowptr_S, order_S = _row_segments(rows[:, 1].contiguous(), xS.shape[0])
-            g = g.detach().to(dt).contiguous()
+            g = _by_value(g.detach().to(dt))
             gT = torch.empty(tuple(xT.shape), dtype=dt, device=dev)
             gS = torch.empty(tuple(xS.shape), dtype=dt, device=dev)
             _lib.check(lib.fc_twin_loss_backward(_ptr(xS), xS.shape[0], _ptr(xT), xT.shape[0], xS.shape[1], _DTYPES[dt], _ptr(p_), P,
@@ -129,7 +129,7 @@ def twin_loss(xS, xT, p_, n_, yN, mu=5):
         raise ValueError('twin_loss: p_ and n_ must each hold at least one pair')
     if not torch.is_tensor(yN) or yN.shape != (n_.shape[0],) or yN.device != dev or not yN.is_floating_point():
         raise ValueError(f'twin_loss: yN must be a ({n_.shape[0]},) floating-point tensor on {dev}')
-    return _TwinLoss.apply(xS, xT, p_, n_, yN.detach().to(torch.float32).contiguous(), float(mu))
+    return _TwinLoss.apply(xS, xT, p_, n_, _by_value(yN.detach().to(torch.float32)), float(mu))
 
 
 def twin_count_dense(xS, xT, thresholds):
@@ -141,7 +141,7 @@ def twin_count_dense(xS, xT, thresholds):
     if not 1 <= len(thr) <= MAX_THRESHOLDS:
         raise ValueError(f'twin_count_dense: between 1 and {MAX_THRESHOLDS} thresholds, got {len(thr)}')
     lib = _lib.load()
-    xSc, xTc = xS.detach().contiguous(), xT.detach().contiguous()
+    xSc, xTc = _by_value(xS.detach()), _by_value(xT.detach())
     T = len(thr)
     with _on(xS.device):
         counts = torch.empty(2 * T, dtype=torch.int64, device=xS.device)
@@ -158,7 +158,7 @@ def twin_eval(xS, xT, p_, n_, thresh):
     dev = xS.device
     n_T, n_S = int(xT.shape[0]), int(xS.shape[0])
     p_ = _pairs(p_, dev, 'twin_eval', 'p_')
-    xSc, xTc = xS.detach().contiguous(), xT.detach().contiguous()
+    xSc, xTc = _by_value(xS.detach()), _by_value(xT.detach())
     thr = torch.tensor(float(thresh), dtype=xS.dtype).item()          # the threshold as the features' dtype holds it
     limit = torch.tensor([n_T - 1, n_S - 1], device=dev)
     zero = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -186,7 +186,8 @@ class _LabelSmoothing(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, weight, conf, off):
         lib = _lib.load()
-        x = pred.detach().contiguous()
+        x = _by_value(pred.detach())
+        weight = None if weight is None else _by_value(weight)
         N, K = int(x.shape[0]), int(x.shape[1])
         dev, dt = x.device, x.dtype
         with _on(dev):
@@ -205,7 +206,7 @@ class _LabelSmoothing(torch.autograd.Function):
         x, target, weight = ctx.saved_tensors
         N, K = int(x.shape[0]), int(x.shape[1])
         with _on(x.device):
-            g = g.detach().to(x.dtype).reshape(1).contiguous()
+            g = _by_value(g.detach().to(x.dtype).reshape(1))
             gpred = torch.empty((N, K), dtype=x.dtype, device=x.device)
             _lib.check(lib.fc_label_smoothing_backward(_ptr(x), _ptr(target), _ptr(weight), _ptr(g), N, K, _DTYPES[x.dtype], ctx.conf,
                                                        ctx.off, _ptr(gpred), _stream()), 'fc_label_smoothing_backward')
@@ -236,5 +237,5 @@ def label_smoothing_loss(pred, target, classes, smoothing=0.0, weight=None):
     if weight is not None:
         if not torch.is_tensor(weight) or weight.shape != (K,) or weight.device != pred.device or not weight.is_floating_point():
             raise ValueError(f'label_smoothing_loss: weight must be a ({K},) floating-point tensor on {pred.device}')
-        weight = weight.detach().to(pred.dtype).contiguous()
+        weight = weight.detach().to(pred.dtype)          # (taken by value in the node)
     return _LabelSmoothing.apply(pred, target.contiguous(), weight, 1.0 - float(smoothing), float(smoothing) / (int(classes) - 1))

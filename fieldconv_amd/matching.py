@@ -7,7 +7,7 @@ or eager path: a CPU tensor raises.  Nothing here is differentiable."""
 import torch
 
 from . import _lib
-from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
+from ._launch import by_value as _by_value, on as _on, ptr as _ptr, scratch as _scratch, stream as _stream, whole as _whole
 from .losses import _DTYPES, _features
 from .pooling import check_ptr, ptr_on
 
@@ -56,7 +56,7 @@ def match_descriptors(xS, xT, k=1, ptr_S=None, ptr_T=None, exclude=None, parts=0
             raise ValueError(f'{what}: rows + 64 * meshes must stay below 2^31')
         ptr_T, ptr_S = ptr_on(ptr_T, host_T, dev), ptr_on(ptr_S, host_S, dev)
     lib = _lib.load()
-    xSc, xTc = xS.detach().contiguous(), xT.detach().contiguous()
+    xSc, xTc = _by_value(xS.detach()), _by_value(xT.detach())
     with _on(dev):
         nbytes = lib.fc_match_workspace_bytes(n_T, k, parts)
         ws = _scratch(nbytes, dev, None)

@@ -9,6 +9,15 @@ from ..functional import field_conv_act, field_conv_params
 from ..graph import get_graph
 
 
+def _as_complex(t):
+    """(..., 2) real pairs as complex numbers, whatever view `t` is: view_as_complex wants unit stride in the pairs, an even storage
+    offset and no lazy negative; anything else is copied first (differentiably)"""
+    t = t.resolve_neg().contiguous()
+    if t.storage_offset() % 2:
+        t = t.clone()
+    return torch.view_as_complex(t)
+
+
 def effective_filter(zonal, spherical, phase, ftype, B):
     """W_eff (O,I,R,2B+1) complex64 with y = <contrib, W_eff> / (2B+1).
 
@@ -18,9 +27,9 @@ def effective_filter(zonal, spherical, phase, ftype, B):
     coefficients as stored (:31).  Differentiable: torch autograd carries the (tiny) chain from the
     kernels' dL/dW_eff back to (zonal, spherical, phase).
     """
-    sph = torch.view_as_complex(spherical)
+    sph = _as_complex(spherical)
     if ftype == 2:
-        zc = torch.view_as_complex(zonal)
+        zc = _as_complex(zonal)
         return torch.cat((sph[..., :B], zc[..., None], sph[..., B:]), dim=3)
     coeff = torch.cat((torch.conj(sph).flip(3), zonal[..., None].to(sph.dtype), sph), dim=3)
     if ftype == 1:

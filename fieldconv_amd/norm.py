@@ -16,7 +16,7 @@ handled as fieldconv_amd.pooling handles it: a MeshBatch's ptr costs no synchron
 import torch
 
 from . import _lib
-from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
+from ._launch import by_value as _by_value, on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
 from .pooling import check_ptr, ptr_on, tag_ptr
 
 _DTYPES = {torch.complex64: 0, torch.complex128: 1}
@@ -27,11 +27,11 @@ class _TangentNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gain, ptr, w, eps):
         lib = _lib.load()
-        xc = x.detach().resolve_conj().resolve_neg().contiguous()
+        xc = _by_value(x.detach())
         N, C, B = int(xc.shape[0]), int(xc.shape[1]), int(ptr.numel()) - 1
         dev, dt, real = xc.device, _DTYPES[xc.dtype], _REAL[xc.dtype]
-        gc = None if gain is None else gain.detach().reshape(-1).contiguous()
-        wc = None if w is None else w.detach().reshape(-1).contiguous()
+        gc = None if gain is None else _by_value(gain.detach().reshape(-1))
+        wc = None if w is None else _by_value(w.detach().reshape(-1))
         with _on(dev):
             nbytes = lib.fc_tangent_norm_workspace_bytes(N, B, C, dt)
             ws = _scratch(nbytes, dev, 1)
@@ -53,7 +53,7 @@ class _TangentNorm(torch.autograd.Function):
         N, C, B, dt, gain_shape = ctx.meta
         dev = x.device
         with _on(dev):
-            gy = gy.detach().to(x.dtype).resolve_conj().resolve_neg().contiguous()
+            gy = _by_value(gy.detach().to(x.dtype))
             nbytes = lib.fc_tangent_norm_workspace_bytes(N, B, C, dt)
             ws = _scratch(nbytes, dev, 1)
             gx = torch.empty((N, C), dtype=x.dtype, device=dev) if need_x else None

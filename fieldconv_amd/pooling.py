@@ -10,7 +10,7 @@ once -- the one synchronisation -- and remembered for as long as the tensor is n
 import torch
 
 from . import _lib
-from ._launch import on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
+from ._launch import by_value as _by_value, on as _on, ptr as _ptr, scratch as _scratch, stream as _stream
 
 _DTYPES = {torch.float32: 0, torch.float64: 1, torch.complex64: 0, torch.complex128: 1}
 _REAL = {torch.complex64: torch.float32, torch.complex128: torch.float64}
@@ -66,7 +66,7 @@ class _MeshPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ptr, reduce, soft_abs):
         lib = _lib.load()
-        xc = x.detach().contiguous()
+        xc = _by_value(x.detach())
         N, C, B = int(xc.shape[0]), int(xc.shape[1]), int(ptr.numel()) - 1
         dev, dt = xc.device, _DTYPES[xc.dtype]
         rdt = _REAL[xc.dtype] if soft_abs else xc.dtype
@@ -88,7 +88,7 @@ class _MeshPool(torch.autograd.Function):
         N, C, B, dt, reduce, soft_abs, xdt = ctx.meta
         dev = ptr.device
         with _on(dev):
-            g = g.detach().to(_REAL[xdt] if soft_abs else xdt).contiguous()
+            g = _by_value(g.detach().to(_REAL[xdt] if soft_abs else xdt))
             gx = torch.empty((N, C), dtype=xdt, device=dev)
             if soft_abs:
                 _lib.check(lib.fc_segment_pool_soft_abs_backward(_ptr(x), _ptr(g), _ptr(ptr), N, B, C, dt, reduce, _ptr(gx), _stream()),
@@ -126,7 +126,7 @@ class _MeshMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ptr):
         lib = _lib.load()
-        xc = x.detach().resolve_conj().resolve_neg().contiguous()
+        xc = _by_value(x.detach())
         N, C, B = int(xc.shape[0]), int(xc.shape[1]), int(ptr.numel()) - 1
         dev, dt, cplx = xc.device, _DTYPES[xc.dtype], int(xc.is_complex())
         rdt = _REAL[xc.dtype] if cplx else xc.dtype
@@ -150,7 +150,7 @@ class _MeshMax(torch.autograd.Function):
         N, C, B, dt, cplx, xdt = ctx.meta
         dev = ptr.device
         with _on(dev):
-            g = g.detach().to(_REAL[xdt] if cplx else xdt).contiguous()
+            g = _by_value(g.detach().to(_REAL[xdt] if cplx else xdt))
             gx = torch.empty((N, C), dtype=xdt, device=dev)
             _lib.check(lib.fc_segment_max_backward(_ptr(x), _ptr(g), _ptr(index), _ptr(ptr), N, B, C, dt, cplx, _ptr(gx), _stream()),
                        'fc_segment_max_backward')

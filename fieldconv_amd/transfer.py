@@ -19,7 +19,7 @@ weight and phase are geometry: they never receive a gradient."""
 import torch
 
 from . import _lib
-from ._launch import device_of as _device_of, on as _on, ptr as _ptr, stream as _stream, whole as _whole
+from ._launch import by_value as _by_value, device_of as _device_of, on as _on, ptr as _ptr, stream as _stream, whole as _whole
 from .geodesic import _batch_tables, _check_diagonals, _check_index, _check_mesh, _segment_sum, mesh_edge_graph, nearest_sample
 from .logmap import _check_bound, log_map_transport
 
@@ -147,14 +147,14 @@ class _TangentTransfer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, plan):
         ctx.plan = plan
-        return _launch(x.detach().resolve_conj().resolve_neg().contiguous(), plan)
+        return _launch(_by_value(x.detach()), plan)
 
     @staticmethod
     def backward(ctx, g):
         if not ctx.needs_input_grad[0]:
             return None, None
         plan = ctx.plan
-        g = g.detach().resolve_conj().resolve_neg().contiguous()
+        g = _by_value(g.detach())
         return _launch(g, plan.adjoint()), None          # d/dx of Re<gy, T x> is T^H gy: the same kernel on the transposed CSR
 
 
@@ -190,7 +190,7 @@ class _TangentTransferMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, plan):
         lib = _lib.load()
-        x = x.detach().resolve_conj().resolve_neg().contiguous()
+        x = _by_value(x.detach())
         dt, cplx = _DTYPES[x.dtype]
         C = int(x.shape[1])
         csr = plan._fwd
@@ -212,7 +212,7 @@ class _TangentTransferMax(torch.autograd.Function):
         lib = _lib.load()
         plan = ctx.plan
         arg, = ctx.saved_tensors
-        g = g.detach().resolve_conj().resolve_neg().contiguous()
+        g = _by_value(g.detach())
         dt, cplx = _DTYPES[g.dtype]
         C = int(g.shape[1])
         csr = plan._bwd
