@@ -164,8 +164,8 @@ int fc_backward_data(const float* x, const float* gy, const float* sten_s, const
     const int rc = check_bwd(x, gy, sten_s, by_source, wpk_bwd, gx, dims);
     if (rc != FC_OK) return rc;
     if (dims->E > 0 && !by_source->nbr) return FC_ERR_BAD_ARGUMENT;
-    return fc::backward_data_impl(x, gy, sten_s, by_source, wpk_bwd, gx, workspace, workspace_bytes, dims, false,
-                                  static_cast<hipStream_t>(stream));
+    return fc::backward_data_impl(x, gy, sten_s, by_source, wpk_bwd, gx, workspace, workspace_bytes, dims, fc::Drive::kDenseRows,
+                                  static_cast<hipStream_t>(stream), fc::GxSum::kInPass);
 }
 
 int fc_backward_data_factored(const float* x, const float* gy, const float* rec_s, const fc_csr* by_source,
@@ -176,18 +176,18 @@ int fc_backward_data_factored(const float* x, const float* gy, const float* rec_
     if (dims->E > 0 && !by_source->runs) return FC_ERR_BAD_ARGUMENT;
     if (dims->R > 8 || !fc::rows_fit_32bit(dims)) return FC_ERR_UNSUPPORTED;
     (void)records;
-    return fc::backward_data_impl(x, gy, rec_s, by_source, wpk_bwd, gx, workspace, workspace_bytes, dims, true,
-                                  static_cast<hipStream_t>(stream));
+    return fc::backward_data_impl(x, gy, rec_s, by_source, wpk_bwd, gx, workspace, workspace_bytes, dims, fc::Drive::kRecords,
+                                  static_cast<hipStream_t>(stream), fc::GxSum::kInPass);
 }
 
 int fc_backward_filter(const float* x, void* workspace, size_t workspace_bytes, const fc_dims* dims, int32_t records, void* stream) {
     if (!x || !fc::dims_valid(dims)) return FC_ERR_BAD_ARGUMENT;
     if (!fc::dims_supported(dims)) return FC_ERR_UNSUPPORTED;
-    return fc::backward_filter_impl(x, workspace, workspace_bytes, dims, static_cast<hipStream_t>(stream), records != 0);
+    return fc::backward_filter_impl(x, workspace, workspace_bytes, dims, fc::drive_of(records), static_cast<hipStream_t>(stream));
 }
 
 int32_t fc_backward_streams(const fc_dims* dims, int32_t records) {
-    return (fc::dims_supported(dims) && dims->R <= 8 && fc::rows_fit_32bit(dims) && fc::backward_streams(dims, records != 0)) ? 1 : 0;
+    return (fc::dims_supported(dims) && dims->R <= 8 && fc::rows_fit_32bit(dims) && fc::backward_streams(dims, fc::drive_of(records))) ? 1 : 0;
 }
 
 int fc_backward_gather(const float* gy, const float* rec_s, const fc_csr* by_source, const float* wpk_bwd, void* workspace,
@@ -196,7 +196,7 @@ int fc_backward_gather(const float* gy, const float* rec_s, const fc_csr* by_sou
     if (dims->E > 0 && (!rec_s || !by_source->runs)) return FC_ERR_BAD_ARGUMENT;
     if (!fc_backward_streams(dims, 1)) return FC_ERR_UNSUPPORTED;
     return fc::backward_stream_impl(nullptr, gy, rec_s, by_source, wpk_bwd, nullptr, workspace, workspace_bytes, dims,
-                                    static_cast<hipStream_t>(stream), 1);
+                                    static_cast<hipStream_t>(stream), fc::StreamStages::kGather);
 }
 
 int fc_backward_stream(const float* x, const float* wpk_bwd, float* gx, void* workspace, size_t workspace_bytes, const fc_dims* dims,
@@ -204,13 +204,13 @@ int fc_backward_stream(const float* x, const float* wpk_bwd, float* gx, void* wo
     if (!x || !wpk_bwd || !gx || !fc::dims_valid(dims)) return FC_ERR_BAD_ARGUMENT;
     if (!fc_backward_streams(dims, 1)) return FC_ERR_UNSUPPORTED;
     return fc::backward_stream_impl(x, nullptr, nullptr, nullptr, wpk_bwd, gx, workspace, workspace_bytes, dims,
-                                    static_cast<hipStream_t>(stream), 2);
+                                    static_cast<hipStream_t>(stream), fc::StreamStages::kStream);
 }
 
 int fc_backward_finish(float* gw_eff, void* workspace, size_t workspace_bytes, const fc_dims* dims, int32_t records, void* stream) {
     if (!gw_eff || !fc::dims_valid(dims)) return FC_ERR_BAD_ARGUMENT;
     if (!fc::dims_supported(dims)) return FC_ERR_UNSUPPORTED;
-    return fc::backward_finish_impl(gw_eff, workspace, workspace_bytes, dims, static_cast<hipStream_t>(stream), records != 0);
+    return fc::backward_finish_impl(gw_eff, workspace, workspace_bytes, dims, fc::drive_of(records), static_cast<hipStream_t>(stream));
 }
 
 static int check_finish_params(const fc_filter_params* params, const fc_dims* dims) {
@@ -230,8 +230,7 @@ int fc_backward_finish_params(float* gw_eff, void* workspace, size_t workspace_b
         if (rc != FC_OK) return rc;
     }
     // the partials' fixed-order sum and the parameter-gradient chain in ONE launch (FC_SPLIT_FINISH=1: the two kernels)
-    static const bool split_finish = [] { const char* e = fc::dev_env("FC_SPLIT_FINISH"); return e && atoi(e) != 0; }();
-    if (split_finish) {
+    if (fc::split_finish()) {
         if (!gw_eff) return FC_ERR_BAD_ARGUMENT;        // (the two-kernel development variant passes gW_eff from one to the other)
         int rc = fc_backward_finish(gw_eff, workspace, workspace_bytes, dims, records, stream);
         if (rc != FC_OK) return rc;
@@ -240,8 +239,8 @@ int fc_backward_finish_params(float* gw_eff, void* workspace, size_t workspace_b
         if (rc != FC_OK || !params->bias_partials) return rc;
         return fc::bias_partials_reduce_impl(params->bias_partials, params->bias_nparts, dims->O, params->g_bias, static_cast<hipStream_t>(stream));
     }
-    return fc::backward_finish_params_impl(gw_eff, workspace, workspace_bytes, dims, params, static_cast<hipStream_t>(stream), 0, 0, 0, nullptr,
-                                           records != 0);
+    return fc::backward_finish_params_impl(gw_eff, workspace, workspace_bytes, dims, fc::drive_of(records), *params, fc::FilterBlock{},
+                                           fc::DeferredGx{}, static_cast<hipStream_t>(stream));
 }
 
 int fc_backward_all(const float* x, const float* gy, const float* sten_or_rec_s, const fc_csr* by_source, int32_t records,
@@ -250,8 +249,7 @@ int fc_backward_all(const float* x, const float* gy, const float* sten_or_rec_s,
     if (!gw_eff && !params) return FC_ERR_BAD_ARGUMENT;         // with parameters gW_eff is optional: nullptr = not wanted
     // With parameters the pass ends in ONE launch (fc_backward_finish_params' kernel): when tiles are shared, the sum of the data kernel's
     // partial gx arrays rides there too instead of a launch of its own between the kernels (nobody reads gx before this call returns)
-    static const bool split_finish = [] { const char* e = fc::dev_env("FC_SPLIT_FINISH"); return e && atoi(e) != 0; }();
-    const bool defer = params != nullptr && !split_finish;
+    const bool defer = params != nullptr && !fc::split_finish();
     int rc = check_bwd(x, gy, sten_or_rec_s, by_source, wpk_bwd, gx, dims);
     if (rc != FC_OK) return rc;
     if (params) {           // before anything is enqueued: a bad params struct must not leave gx half-finished in the workspace
@@ -262,15 +260,15 @@ int fc_backward_all(const float* x, const float* gy, const float* sten_or_rec_s,
         if (dims->E > 0 && !by_source->runs) return FC_ERR_BAD_ARGUMENT;
         if (dims->R > 8 || !fc::rows_fit_32bit(dims)) return FC_ERR_UNSUPPORTED;
     } else if (dims->E > 0 && !by_source->nbr) return FC_ERR_BAD_ARGUMENT;
-    rc = fc::backward_data_impl(x, gy, sten_or_rec_s, by_source, wpk_bwd, gx, workspace, workspace_bytes, dims, records != 0,
-                                static_cast<hipStream_t>(stream), defer);
+    rc = fc::backward_data_impl(x, gy, sten_or_rec_s, by_source, wpk_bwd, gx, workspace, workspace_bytes, dims, fc::drive_of(records),
+                                static_cast<hipStream_t>(stream), defer ? fc::GxSum::kDeferred : fc::GxSum::kInPass);
     if (rc != FC_OK) return rc;
     rc = fc_backward_filter(x, workspace, workspace_bytes, dims, records, stream);
     if (rc != FC_OK) return rc;
     if (!params) return fc_backward_finish(gw_eff, workspace, workspace_bytes, dims, records, stream);
     if (!defer) return fc_backward_finish_params(gw_eff, workspace, workspace_bytes, dims, records, params, stream);
-    return fc::backward_finish_params_impl(gw_eff, workspace, workspace_bytes, dims, params, static_cast<hipStream_t>(stream), 0, 0, 0, gx,
-                                           records != 0, x);
+    return fc::backward_finish_params_impl(gw_eff, workspace, workspace_bytes, dims, fc::drive_of(records), *params, fc::FilterBlock{},
+                                           fc::DeferredGx{gx, x}, static_cast<hipStream_t>(stream));
 }
 
 int fc_forward_params(const float* x, const float* sten_or_records, const fc_csr* by_target, int32_t kind,

@@ -372,7 +372,6 @@ __global__ __launch_bounds__(kThreads) void fc_backward_filter_half2_kernel(
     for (int n = 0; n < T; ++n) { gre[n] = f32x4{0.f, 0.f, 0.f, 0.f}; gim[n] = gre[n]; }
 
     const int nchunk = KP / 4;                     // chunks of four k entries; a lane holds chunks lane and lane + 64 of its vertex's row
-    // registers one slab ahead: my vertex's row of H (fp32) and the scales behind the slab
     // Registers one slab ahead: my vertex's row of H and the scales behind the slab.  (A second set, two slabs ahead, does not
     // fit the 128 registers -- and would not pay: with the rows of ONE tile re-read from L2 all the time, FC_DEBUG_BWD=16, the
     // kernel takes 73.0 instead of 74.5 us; it does not wait for HBM.)
@@ -544,7 +543,7 @@ __global__ __launch_bounds__(kThreads) void fc_backward_filter_half2_kernel(
                 for (int jj = 0; jj < 4; ++jj) ggwp[base + (4 * fq + jj) * 16 + fr] = make_float2(xr[jj] * it, xi[jj] * it);
             }
         }
-    
+
     };
     int buf = 0;
     for (int tile = blockIdx.x; tile < a.ntiles; tile += tile_step, buf ^= 1) {
@@ -625,28 +624,20 @@ static int launch_gather(const float2* gy, const float* rec, const fc_csr* g, co
 template <int T, int KPT = 0, int IT = 0>
 static int launch_stream(const float2* x, const char* hrec, const float* wpk, float2* gwp, float2* gxt, const StreamArgs& a,
                          const StreamPlan& p, hipStream_t stream) {
-    auto kern = fc_backward_stream_kernel<T, KPT, IT>;
     static bool lds_ok[kMaxDevices] = {};
-    if (!allow_full_lds(reinterpret_cast<const void*>(kern), p.lds, lds_ok)) return FC_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(p.P, p.FS), dim3(kThreads), p.lds, stream, x, hrec, wpk, gwp, gxt, a);
-    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+    return launch_full_lds(fc_backward_stream_kernel<T, KPT, IT>, lds_ok, dim3(p.P, p.FS), p.lds, stream, x, hrec, wpk, gwp, gxt, a);
 }
 
-// stage bits: 1 the gather kernel, 2 the streaming kernel + gx (fc_backward_gather / fc_backward_stream time them apart), 4 without the gx
-// kernel (fc_backward_all with module parameters: the finishing launch forms gx)
-int backward_stream_impl(const float* x, const float* gy, const float* rec, const fc_csr* g, const float* wpk, float* gx, void* ws,
-                         size_t ws_bytes, const fc_dims* d, hipStream_t stream, int stages) {
-    const StreamPlan p = plan_stream(d, halves_of(d), true);
-    if (!p.ok) return FC_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < p.hrec_bytes + p.gwp_bytes + p.gxt_bytes + p.wst_bytes) return FC_ERR_WORKSPACE;
+// gx_sum == kDeferred: without the gx kernel (fc_backward_all with module parameters: the finishing launch forms gx)
+static int stream_launches(const BackwardRoute& r, const float* x, const float* gy, const float* rec, const fc_csr* g, const float* wpk,
+                           float* gx, const fc_dims* d, hipStream_t stream, StreamStages stages, GxSum gx_sum) {
+    const StreamPlan& p = r.stream;
+    const auto [hrec, gwp, gxt, wst] = r.sw;
     StreamArgs a = make_stream_args(d, p);
-    char* hrec = static_cast<char*>(ws);
-    a.wst = reinterpret_cast<uint32_t*>(hrec + p.hrec_bytes + p.gwp_bytes + p.gxt_bytes);      // (16-byte aligned: the three sizes before it are)
-    float2* gwp = reinterpret_cast<float2*>(hrec + p.hrec_bytes);
-    float2* gxt = reinterpret_cast<float2*>(hrec + p.hrec_bytes + p.gwp_bytes);
+    a.wst = wst;
     const float2* x2 = reinterpret_cast<const float2*>(x);
     int rc = FC_ERR_UNSUPPORTED;
-    if (stages & 1) {
+    if (stages != StreamStages::kStream) {
         const float2* gy2 = reinterpret_cast<const float2*>(gy);
 #define FC_GATHER_CASE(RR, BB) if (d->R == RR && d->B == BB) rc = launch_gather<RR, BB>(gy2, rec, g, wpk, hrec, a, p, stream);
         FC_GATHER_CASE(2, 1) FC_GATHER_CASE(4, 1) FC_GATHER_CASE(6, 1) FC_GATHER_CASE(8, 1)
@@ -655,13 +646,13 @@ int backward_stream_impl(const float* x, const float* gy, const float* rec, cons
 #undef FC_GATHER_CASE
         if (rc != FC_OK) return rc;
     }
-    if (!(stages & 2)) return FC_OK;
+    if (stages == StreamStages::kGather) return FC_OK;
     if (p.T == 6 && p.KPS == 288 && d->I == 48) rc = launch_stream<6, 288, 48>(x2, hrec, wpk, gwp, gxt, a, p, stream);      // the reference's default layer
     else if (p.T == 6 && p.KPS == 192 && d->I == 64) rc = launch_stream<6, 192, 64>(x2, hrec, wpk, gwp, gxt, a, p, stream);  // config 5's layer: a half of 64 x 6 entries
     else if (p.T <= 2) rc = launch_stream<2>(x2, hrec, wpk, gwp, gxt, a, p, stream);
     else if (p.T <= 4) rc = launch_stream<4>(x2, hrec, wpk, gwp, gxt, a, p, stream);
     else rc = launch_stream<6>(x2, hrec, wpk, gwp, gxt, a, p, stream);
-    if (rc != FC_OK || (stages & 4)) return rc;         // (4: gx is left to the launch that finishes the pass)
+    if (rc != FC_OK || gx_sum == GxSum::kDeferred) return rc;
     const size_t count = (size_t)d->N * d->I;
     const dim3 grid((unsigned)((count + 255) / 256));
     float2* gx2 = reinterpret_cast<float2*>(gx);
@@ -671,55 +662,43 @@ int backward_stream_impl(const float* x, const float* gy, const float* rec, cons
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
-bool backward_streams(const fc_dims* d, bool factored) { return plan_stream(d, halves_of(d), factored).ok; }
+int backward_stream_impl(const float* x, const float* gy, const float* rec, const fc_csr* g, const float* wpk, float* gx, void* ws,
+                         size_t ws_bytes, const fc_dims* d, hipStream_t stream, StreamStages stages) {
+    const BackwardRoute r = backward_route(d, Drive::kRecords, ws, ws_bytes);
+    if (!r.streams || r.status != FC_OK) return r.streams ? r.status : FC_ERR_UNSUPPORTED;
+    return stream_launches(r, x, gy, rec, g, wpk, gx, d, stream, stages, GxSum::kInPass);
+}
 
+bool backward_streams(const fc_dims* d, Drive drive) { return plan_stream(d, halves_of(d), drive == Drive::kRecords).ok; }
 bool backward_fits(const fc_dims* d) { return plan_backward(d, halves_of(d)).ok_factored; }
 
 size_t backward_workspace_bytes(const fc_dims* d) {
-    const BwdPlan p = plan_backward(d, halves_of(d));
-    const size_t pair = p.hdump_bytes + p.gwp_bytes + p.gxp_bytes + 256;
+    const size_t pair = carved_bytes(pair_workspace, plan_backward(d, halves_of(d)));
     const StreamPlan sp = plan_stream(d, halves_of(d), true);          // (records or not is the launch's choice: room for either)
-    const size_t stream = sp.ok ? sp.hrec_bytes + sp.gwp_bytes + sp.gxt_bytes + sp.wst_bytes + 256 : 0;
-    return pair > stream ? pair : stream;
+    const size_t stream = sp.ok ? carved_bytes(stream_workspace, sp) : 0;
+    return (pair > stream ? pair : stream) + 256;      // + 256: slack the callers have always been told about; no layout hands it out, no check asks for it
 }
 
 template <int T>
 static int launch_backward_filter(const float2* x, const float* hdump, float2* gwp, const BwdArgs& a, const BwdPlan& p,
                                   const fc_dims* d, hipStream_t stream) {
-    static const bool half2 = !(dev_env("FC_FILTER2") && atoi(dev_env("FC_FILTER2")) == 0);      // FC_FILTER2=0: the LDS-staged kernel (development)
-    static bool ok_half2[kMaxDevices] = {}, ok_half[kMaxDevices] = {}, ok_f32[kMaxDevices] = {};      // per T (this function is a template)
-    if (p.fhalf && half2) {
-        const size_t lds2 = (size_t)(2 * kTile * filter_image_stride(p.KP) + 2 * 6 * p.IP * kXbStride + 8) * sizeof(_Float16) + 16;
-        static bool ok_half2h[kMaxDevices] = {};
-        if (a.dump_halves) {
-            if (!allow_full_lds(reinterpret_cast<const void*>(fc_backward_filter_half2_kernel<T, true>), lds2, ok_half2h)) return FC_ERR_LAUNCH;
-            hipLaunchKernelGGL((fc_backward_filter_half2_kernel<T, true>), dim3(p.P, p.F), dim3(kThreads), lds2, stream, x, hdump, gwp, a, p.F,
-                               d->B, d->R * d->O);
-        } else {
-            if (!allow_full_lds(reinterpret_cast<const void*>(fc_backward_filter_half2_kernel<T, false>), lds2, ok_half2)) return FC_ERR_LAUNCH;
-            hipLaunchKernelGGL((fc_backward_filter_half2_kernel<T, false>), dim3(p.P, p.F), dim3(kThreads), lds2, stream, x, hdump, gwp, a, p.F,
-                               d->B, d->R * d->O);
-        }
-    } else if (p.fhalf) {
-        if (!allow_full_lds(reinterpret_cast<const void*>(fc_backward_filter_half_kernel<T>), p.lds_filter, ok_half)) return FC_ERR_LAUNCH;
-        hipLaunchKernelGGL(fc_backward_filter_half_kernel<T>, dim3(p.P, p.F), dim3(kThreads), p.lds_filter, stream, x, hdump, gwp, a,
-                           p.F, d->B, d->R * d->O);
-    } else {
-        if (!allow_full_lds(reinterpret_cast<const void*>(fc_backward_filter_kernel<T>), p.lds_filter, ok_f32)) return FC_ERR_LAUNCH;
-        hipLaunchKernelGGL(fc_backward_filter_kernel<T>, dim3(p.P, p.F), dim3(kThreads), p.lds_filter, stream, x, hdump, gwp, a, p.F,
-                           d->B);
-    }
-    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+    static bool ok[4][kMaxDevices] = {};      // per kernel, and per T (this function is a template)
+    const int KV = d->R * d->O;      // (p.lds_filter: of the variant that plan_backward and the FC_FILTER2 switch select)
+    if (p.fhalf && !filter_staged())
+        return a.dump_halves ? launch_full_lds(fc_backward_filter_half2_kernel<T, true>, ok[0], dim3(p.P, p.F), p.lds_filter, stream, x, hdump, gwp, a, p.F, d->B, KV)
+                             : launch_full_lds(fc_backward_filter_half2_kernel<T, false>, ok[1], dim3(p.P, p.F), p.lds_filter, stream, x, hdump, gwp, a, p.F, d->B, KV);
+    if (p.fhalf) return launch_full_lds(fc_backward_filter_half_kernel<T>, ok[2], dim3(p.P, p.F), p.lds_filter, stream, x, hdump, gwp, a, p.F, d->B, KV);
+    return launch_full_lds(fc_backward_filter_kernel<T>, ok[3], dim3(p.P, p.F), p.lds_filter, stream, x, hdump, gwp, a, p.F, d->B);
 }
 
-int backward_filter_impl(const float* x, void* ws, size_t ws_bytes, const fc_dims* d, hipStream_t stream, bool factored) {
-    if (backward_streams(d, factored)) return FC_OK;        // (the streaming kernel behind the gather has left the partials already)
-    const BwdPlan p = plan_backward(d, halves_of(d));
-    if (!p.ok) return FC_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < p.hdump_bytes + p.gwp_bytes) return FC_ERR_WORKSPACE;
+int backward_filter_impl(const float* x, void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, hipStream_t stream) {
+    const BackwardRoute r = backward_route(d, drive, ws, ws_bytes);
+    if (r.streams) return FC_OK;        // (the streaming kernel behind the gather has left the partials already)
+    if (r.status != FC_OK) return r.status;
+    const BwdPlan& p = r.pair;
     const BwdArgs a = make_args(d, p);
-    const float* hdump = reinterpret_cast<const float*>(ws);
-    float2* gwp = reinterpret_cast<float2*>(static_cast<char*>(ws) + p.hdump_bytes);
+    const float* hdump = r.pw.hdump;
+    float2* gwp = r.pw.gwp;
     const float2* x2 = reinterpret_cast<const float2*>(x);
     int need = (p.ngw + kWaves - 1) / kWaves;
     if (p.fhalf) {      // column-grouped assignment: the wavefronts of the smallest column group bound the slot count
@@ -735,24 +714,21 @@ int backward_filter_impl(const float* x, void* ws, size_t ws_bytes, const fc_dim
 
 // Which kernels a backward pass with these dims launches (fc_describe_kernels).
 void describe_backward(const fc_dims* d, int records, char* buf, size_t n) {
-    {
-        const StreamPlan sp = plan_stream(d, halves_of(d), records != 0);
-        if (sp.ok) {
-            snprintf(buf, n, "fc_backward_gather_kernel<records,split-f16> tiles=%d (%d workgroups of %d wavefronts, %d per SIMD); fc_backward_stream_kernel (H once for gxt and gW: %d gxt + %d gW "
-                     "wavefronts, W_f in registers, records by LDS-DMA) grid=%dx%d; fc_backward_gx_kernel; module parameters: "
-                     "fc_backward_finish_params (sum of the partials + parameter chain) in one launch; explicit filter: fc_backward_finish; cus=%d",
-                     sp.ntiles, sp.ggrid, sp.gwpg, sp.gwaves, sp.G, sp.NW, sp.P, sp.FS, num_cus());
-            return;
-        }
+    const BackwardRoute r = backward_route(d, drive_of(records), nullptr, 0);        // (the route the launches take; no buffer, status unused)
+    if (r.streams) {
+        const StreamPlan& sp = r.stream;
+        snprintf(buf, n, "fc_backward_gather_kernel<records,split-f16> tiles=%d (%d workgroups of %d wavefronts, %d per SIMD); fc_backward_stream_kernel (H once for gxt and gW: %d gxt + %d gW "
+                 "wavefronts, W_f in registers, records by LDS-DMA) grid=%dx%d; fc_backward_gx_kernel; module parameters: "
+                 "fc_backward_finish_params (sum of the partials + parameter chain) in one launch; explicit filter: fc_backward_finish; cus=%d",
+                 sp.ntiles, sp.ggrid, sp.gwpg, sp.gwaves, sp.G, sp.NW, sp.P, sp.FS, num_cus());
+        return;
     }
-    const BwdPlan p = plan_backward(d, halves_of(d));
+    const BwdPlan& p = r.pair;
     const char* mode = halves_of(d) == 2 ? "split-f16" : halves_of(d) == 1 ? "f16" : "f32";
-    static const bool staged = [] { const char* e = dev_env("FC_FILTER2"); return e && atoi(e) == 0; }();
-    static const bool split_finish = [] { const char* e = dev_env("FC_SPLIT_FINISH"); return e && atoi(e) != 0; }();
     // what ends the pass follows the same switches the launches use (fc_api.hip: fc_backward_all / fc_backward_finish_params)
     const int gx_parts = (1 << p.parts_log2) * (p.gsplit ? 2 : 1);
     char fin[320];
-    if (split_finish)
+    if (split_finish())
         snprintf(fin, sizeof(fin), "%sfc_backward_finish + fc_filter_param_grads (two launches: the split-finish development switch)",
                  gx_parts > 1 ? "fc_sum_parts_kernel (the partial gx arrays), " : "");
     else
@@ -761,75 +737,50 @@ void describe_backward(const fc_dims* d, int records, char* buf, size_t n) {
                  gx_parts > 1 ? " + sum of the partial gx arrays" : "", gx_parts > 1 ? "fc_sum_parts_kernel, " : "");
     snprintf(buf, n, "fc_backward_data_kernel<%s,%s> tiles=%d parts=%d%s; %s; %s; cus=%d", records ? "records" : "dense rows", mode, p.ntiles,
              1 << p.parts_log2, p.gsplit ? " (the two frequency groups of a tile as separate work items)" : "",
-             p.fhalf ? (staged ? "fc_backward_filter_half_kernel (LDS-staged slabs)" : "fc_backward_filter_half2_kernel (register-fed rows)")
+             p.fhalf ? (filter_staged() ? "fc_backward_filter_half_kernel (LDS-staged slabs)" : "fc_backward_filter_half2_kernel (register-fed rows)")
                      : "fc_backward_filter_kernel (fp32 MFMA)",
              fin, num_cus());
 }
 
-// Fixed-order sum of the per-workgroup filter-gradient partials left in the workspace.
-int backward_finish_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, hipStream_t stream, bool factored) {
-    {
-        const StreamPlan sp = plan_stream(d, halves_of(d), factored);
-        if (sp.ok) {        // partials [P][F][k = o*R + r][IP]
-            if (!ws || ws_bytes < sp.hrec_bytes + sp.gwp_bytes) return FC_ERR_WORKSPACE;
-            const float2* gwp = reinterpret_cast<const float2*>(static_cast<char*>(ws) + sp.hrec_bytes);
-            const int total = sp.F * d->R * d->O * d->I;
-            hipLaunchKernelGGL(fc_reduce_gw_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, gwp, reinterpret_cast<float2*>(gw_eff),
-                               sp.P, sp.F, d->R, d->O, d->I, sp.KP, sp.IP, 2);
-            return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
-        }
-    }
-    const BwdPlan p = plan_backward(d, halves_of(d));
-    if (!p.ok) return FC_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < p.hdump_bytes + p.gwp_bytes) return FC_ERR_WORKSPACE;
-    const float2* gwp = reinterpret_cast<const float2*>(static_cast<char*>(ws) + p.hdump_bytes);
-    const int total = p.F * d->R * d->O * d->I;
-    hipLaunchKernelGGL(fc_reduce_gw_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, gwp,
-                       reinterpret_cast<float2*>(gw_eff), p.P, p.F, d->R, d->O, d->I, p.KP, p.IP, p.gd.split != 0 ? 1 : 0);
+// Fixed-order sum of the per-workgroup filter-gradient partials [P][F][k][IP] left in the workspace.
+int backward_finish_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, hipStream_t stream) {
+    const BackwardRoute r = backward_route(d, drive, ws, ws_bytes);
+    if (r.status != FC_OK) return r.status;
+    const int F = r.streams ? r.stream.F : r.pair.F, KP = r.streams ? r.stream.KP : r.pair.KP, IP = r.streams ? r.stream.IP : r.pair.IP;
+    const int total = F * d->R * d->O * d->I;
+    hipLaunchKernelGGL(fc_reduce_gw_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const float2*>(r.partials.gwp),
+                       reinterpret_cast<float2*>(gw_eff), r.partials.P, F, d->R, d->O, d->I, KP, IP, r.streams ? 2 : r.partials.ring_pairs ? 1 : 0);
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
-int backward_finish_params_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, const fc_filter_params* fp, hipStream_t stream,
-                                int o0, int i0, int Ifull, float* gx_deferred, bool factored, const float* x_for_gx) {
-    {
-        const StreamPlan sp = plan_stream(d, halves_of(d), factored);
-        if (sp.ok) {        // partial (p, f, k = o*R + r, i) at ((p*F + f)*KP + k)*IP + i
-            if (!ws || ws_bytes < sp.hrec_bytes + sp.gwp_bytes + sp.gxt_bytes) return FC_ERR_WORKSPACE;
-            const float* gwp = reinterpret_cast<const float*>(static_cast<char*>(ws) + sp.hrec_bytes);
-            // gx_deferred (fc_backward_all): the gx kernel was left out -- gx is formed from the gxt slices by extra workgroups of this launch
-            const bool ride = gx_deferred && x_for_gx;
-            const float* gxt = reinterpret_cast<const float*>(static_cast<char*>(ws) + sp.hrec_bytes + sp.gwp_bytes);
-            return reduce_param_grads_impl(gwp, (size_t)sp.F * sp.KP * sp.IP, (size_t)sp.IP, (size_t)sp.KP * sp.IP, (size_t)d->R * sp.IP, false, sp.P,
-                                           gw_eff, fp->zonal, fp->spherical, fp->phase, fp->ftype, fp->g_zonal, fp->g_spherical, fp->g_phase, d,
-                                           stream, o0, i0, Ifull, fp->bias_partials, fp->bias_nparts, fp->g_bias, ride ? gxt : nullptr,
-                                           ride ? gx_deferred : nullptr, (size_t)d->N * d->I, 0, ride ? -(d->B + 4 * (sp.KS - 1)) : 0, ride ? x_for_gx : nullptr);
-        }
+int backward_finish_params_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, const fc_filter_params& fp,
+                                const FilterBlock& block, const DeferredGx& deferred, hipStream_t stream) {
+    const BackwardRoute r = backward_route(d, drive, ws, ws_bytes);
+    if (r.status != FC_OK) return r.status;
+    GxRider rider;
+    if (r.streams) {        // the gx kernel was left out: gx is formed from the gxt slices by extra workgroups of this launch
+        if (deferred.gx && deferred.x)
+            rider = {GxRider::kFromSlices, deferred.gx, {}, {reinterpret_cast<const float*>(r.sw.gxt), deferred.x, d->B, r.stream.KS}};
+    } else {                // the data kernel's partial gx arrays, added here
+        const int nparts = deferred.gx ? (1 << r.pair.parts_log2) << r.pair.gsplit : 1;
+        rider = {GxRider::kSumParts, deferred.gx, {nparts > 1 ? r.pw.gxp : nullptr, r.pair.gx_part_stride, nparts}, {}};
     }
-    const BwdPlan p = plan_backward(d, halves_of(d));
-    if (!p.ok) return FC_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < p.hdump_bytes + p.gwp_bytes) return FC_ERR_WORKSPACE;
-    const float* gwp = reinterpret_cast<const float*>(static_cast<char*>(ws) + p.hdump_bytes);
-    // the data kernel's partial gx arrays (backward_data_impl with defer_gx_sum), added here
-    const int gx_nparts = gx_deferred ? (1 << p.parts_log2) << p.gsplit : 1;
-    const float* gxp = gx_nparts > 1 ? reinterpret_cast<const float*>(static_cast<char*>(ws) + p.hdump_bytes + p.gwp_bytes) : nullptr;
-    // partial (p, f, k = r*O + o, i) at ((p*F + f)*KP + k)*IP + i
-    return reduce_param_grads_impl(gwp, (size_t)p.F * p.KP * p.IP, (size_t)d->O * p.IP, (size_t)p.KP * p.IP, (size_t)p.IP, p.gd.split != 0, p.P, gw_eff,
-                                   fp->zonal, fp->spherical, fp->phase, fp->ftype, fp->g_zonal, fp->g_spherical, fp->g_phase, d, stream, o0,
-                                   i0, Ifull, fp->bias_partials, fp->bias_nparts, fp->g_bias, gxp, gx_deferred, (size_t)d->N * d->I,
-                                   p.gx_part_stride, gx_nparts);
+    return reduce_param_grads_impl(r.partials, gw_eff, fp, block, rider, d, stream);
 }
 
-#define FC_BWD_DATA_ARGS const float*, const float*, const float*, const fc_csr*, const float*, float*, void*, size_t, const fc_dims*, bool, hipStream_t, bool
+#define FC_BWD_DATA_ARGS const float*, const float*, const float*, const fc_csr*, const float*, float*, const BwdPlan&, const PairWorkspace&, const fc_dims*, Drive, hipStream_t, GxSum
 template int backward_data_impl_mode<false>(FC_BWD_DATA_ARGS);
 extern template int backward_data_impl_mode<true>(FC_BWD_DATA_ARGS);
 
 int backward_data_impl(const float* x, const float* gy, const float* sten, const fc_csr* g, const float* wpk, float* gx,
-                       void* ws, size_t ws_bytes, const fc_dims* d, bool factored, hipStream_t stream, bool defer_gx_sum) {
+                       void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, hipStream_t stream, GxSum gx_sum) {
+    const BackwardRoute r = backward_route(d, drive, ws, ws_bytes);
+    if (r.status != FC_OK) return r.status;
     // large meshes: gather kernel + the kernel that streams H once for gxt and gW + gx -- after this call gx is complete AND the
     // filter-gradient partials are in the workspace (backward_filter_impl has nothing left to do)
-    if (backward_streams(d, factored)) return backward_stream_impl(x, gy, sten, g, wpk, gx, ws, ws_bytes, d, stream, defer_gx_sum ? 7 : 3);
-    return halves_of(d) ? backward_data_impl_mode<true>(x, gy, sten, g, wpk, gx, ws, ws_bytes, d, factored, stream, defer_gx_sum)
-                        : backward_data_impl_mode<false>(x, gy, sten, g, wpk, gx, ws, ws_bytes, d, factored, stream, defer_gx_sum);
+    if (r.streams) return stream_launches(r, x, gy, sten, g, wpk, gx, d, stream, StreamStages::kWholePass, gx_sum);
+    return halves_of(d) ? backward_data_impl_mode<true>(x, gy, sten, g, wpk, gx, r.pair, r.pw, d, drive, stream, gx_sum)
+                        : backward_data_impl_mode<false>(x, gy, sten, g, wpk, gx, r.pair, r.pw, d, drive, stream, gx_sum);
 }
 
 }  // namespace fc

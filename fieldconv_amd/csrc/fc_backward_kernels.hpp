@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
+#include "fc_workspace.hpp"
 #include "fc_tile.hpp"
 
 namespace fc {
@@ -570,7 +571,7 @@ inline BwdPlan plan_backward(const fc_dims* d, int halves) {
     const int stride_tails = round_up(p.slab_floats + 2 * kTile + 2 * p.IP, 256);
     const size_t lds_half = (size_t)(2 * stride_tails + (kTile * filter_image_stride(p.KP) + 6 * p.IP * kXbStride) / 2 + 4) * sizeof(float);
     // (the register-fed half2 kernel needs two images and no fp32 slab in LDS; FC_FILTER2=0 selects the LDS-staged one)
-    static const bool staged = [] { const char* e = dev_env("FC_FILTER2"); return e && atoi(e) == 0; }();
+    const bool staged = filter_staged();
     const size_t lds_half2 = (size_t)(2 * kTile * filter_image_stride(p.KP) + 2 * 6 * p.IP * kXbStride + 8) * sizeof(_Float16) + 16;
     p.fhalf = (halves != 0 && p.IP <= 64 && p.KP <= 512 && (staged ? lds_half : lds_half2) <= kMaxLds) ? 1 : 0;
     p.slab_stride = p.fhalf ? stride_tails : round_up(p.slab_floats, 256);
@@ -583,6 +584,13 @@ inline BwdPlan plan_backward(const fc_dims* d, int halves) {
            kTile * d->I <= kThreads;
     p.ok_factored = p.ok && p.lds_data_factored <= kMaxLds;
     return p;
+}
+
+// The workspace of the data / filter kernel pair: the kept H slabs, the filter kernel's per-workgroup gW partials [P][F][KP][IP], and --
+// only when tiles are shared (edge parts, frequency groups) -- the data kernel's partial gx arrays.  Its size: a null run.
+struct PairWorkspace { float* hdump; float2* gwp; float* gxp; };
+inline PairWorkspace pair_workspace(Carver& c, const BwdPlan& p) {
+    return {c.take_packed<float>(p.hdump_bytes), c.take_packed<float2>(p.gwp_bytes), c.take_packed<float>(p.gxp_bytes)};
 }
 
 inline BwdArgs make_args(const fc_dims* d, const BwdPlan& p) {
@@ -601,8 +609,7 @@ inline BwdArgs make_args(const fc_dims* d, const BwdPlan& p) {
     a.slab_floats = p.slab_floats;
     a.slab_stride = p.slab_stride;
     a.tails = p.fhalf;
-    static const bool staged = [] { const char* e = dev_env("FC_FILTER2"); return e && atoi(e) == 0; }();
-    a.dump_halves = (p.fhalf && p.gd.split == 2 && !staged) ? 1 : 0;
+    a.dump_halves = (p.fhalf && p.gd.split == 2 && !filter_staged()) ? 1 : 0;
     a.nt_dump = p.hdump_bytes > ((size_t)192 << 20) ? 1 : 0;
     static const int dbg = [] { const char* e = dev_env("FC_DEBUG_BWD"); return e ? atoi(e) : 0; }();       // read once per process
     a.dbg = dbg;
@@ -615,53 +622,38 @@ inline BwdArgs make_args(const fc_dims* d, const BwdPlan& p) {
 template <int R, int B, bool FACTORED, bool SPLIT, int NGX = 0>
 static int launch_backward_data(const float2* x, const float2* gy, const float* sten, const fc_csr* g, const float* wpk,
                                 float2* gx, float* hdump, const BwdArgs& a, const BwdPlan& p, hipStream_t stream) {
-    auto kern = fc_backward_data_kernel<R, B, FACTORED, SPLIT, NGX>;
-    const size_t lds = FACTORED ? p.lds_data_factored : p.lds_data;
     static bool lds_ok[kMaxDevices] = {};        // per kernel instantiation (this function is a template)
-    if (!allow_full_lds(reinterpret_cast<const void*>(kern), lds, lds_ok)) return FC_ERR_LAUNCH;
     const int nitems = p.ntiles << p.gsplit;
     const int grid = FACTORED ? (nitems < num_cus() ? nitems : num_cus()) : nitems;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, x, gy, sten, g->rowptr, FACTORED ? g->runs : g->nbr, wpk, gx,
-                       hdump, a);
-    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
+    return launch_full_lds(fc_backward_data_kernel<R, B, FACTORED, SPLIT, NGX>, lds_ok, dim3(grid), FACTORED ? p.lds_data_factored : p.lds_data, stream,
+                           x, gy, sten, g->rowptr, FACTORED ? g->runs : g->nbr, wpk, gx, hdump, a);
 }
 
 template <bool SPLIT>
 int backward_data_impl_mode(const float* x, const float* gy, const float* sten, const fc_csr* g, const float* wpk, float* gx,
-                            void* ws, size_t ws_bytes, const fc_dims* d, bool factored, hipStream_t stream, bool defer_gx_sum) {
-    const BwdPlan p = plan_backward(d, SPLIT ? halves_of(d) : 0);
-    if (!(factored ? p.ok_factored : p.ok)) return FC_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < p.hdump_bytes + p.gwp_bytes + p.gxp_bytes) return FC_ERR_WORKSPACE;
+                            const BwdPlan& p, const PairWorkspace& w, const fc_dims* d, Drive drive, hipStream_t stream, GxSum gx_sum) {
+    const bool factored = drive == Drive::kRecords, defer_gx_sum = gx_sum == GxSum::kDeferred;
     const BwdArgs a = make_args(d, p);
-    float* hdump = reinterpret_cast<float*>(ws);
-    // with an edge split the parts write partial gx arrays behind the slabs and the filter partials
-    float* gxp = reinterpret_cast<float*>(static_cast<char*>(ws) + p.hdump_bytes + p.gwp_bytes);
     const int gx_parts = (1 << p.parts_log2) << p.gsplit;
-    float2* gx2 = reinterpret_cast<float2*>(gx_parts > 1 ? gxp : gx);
+    float2* gx2 = reinterpret_cast<float2*>(gx_parts > 1 ? w.gxp : gx);      // (shared tiles: the parts write partial gx arrays)
+    const float2 *x2 = reinterpret_cast<const float2*>(x), *gy2 = reinterpret_cast<const float2*>(gy);
     int rc = FC_ERR_UNSUPPORTED;
     if constexpr (SPLIT) {
         if (p.ngx == 2 && d->R == 6 && d->B == 2) {      // (bwd_forced_groups)
-            rc = factored ? launch_backward_data<6, 2, true, SPLIT, 2>(reinterpret_cast<const float2*>(x), reinterpret_cast<const float2*>(gy), sten,
-                                                                       g, wpk, gx2, hdump, a, p, stream)
-                          : launch_backward_data<6, 2, false, SPLIT, 2>(reinterpret_cast<const float2*>(x), reinterpret_cast<const float2*>(gy), sten,
-                                                                        g, wpk, gx2, hdump, a, p, stream);
+            rc = factored ? launch_backward_data<6, 2, true, SPLIT, 2>(x2, gy2, sten, g, wpk, gx2, w.hdump, a, p, stream)
+                          : launch_backward_data<6, 2, false, SPLIT, 2>(x2, gy2, sten, g, wpk, gx2, w.hdump, a, p, stream);
             if (rc != FC_OK || defer_gx_sum) return rc;
-            return sum_parts(gxp, gx, (size_t)d->N * d->I, p.gx_part_stride, gx_parts, stream);
+            return sum_parts(w.gxp, gx, (size_t)d->N * d->I, p.gx_part_stride, gx_parts, stream);
         }
     }
-#define FC_CASE(RR, BB)                                                                                                \
-    if (d->R == RR && d->B == BB)                                                                                      \
-        rc = factored ? launch_backward_data<RR, BB, true, SPLIT>(reinterpret_cast<const float2*>(x),                  \
-                                                           reinterpret_cast<const float2*>(gy), sten, g, wpk, gx2,     \
-                                                           hdump, a, p, stream)                                        \
-                      : launch_backward_data<RR, BB, false, SPLIT>(reinterpret_cast<const float2*>(x),                 \
-                                                            reinterpret_cast<const float2*>(gy), sten, g, wpk, gx2,    \
-                                                            hdump, a, p, stream);
+#define FC_CASE(RR, BB)                                                                                       \
+    if (d->R == RR && d->B == BB)                                                                             \
+        rc = factored ? launch_backward_data<RR, BB, true, SPLIT>(x2, gy2, sten, g, wpk, gx2, w.hdump, a, p, stream) \
+                      : launch_backward_data<RR, BB, false, SPLIT>(x2, gy2, sten, g, wpk, gx2, w.hdump, a, p, stream);
     FC_FOR_EACH_SHAPE(FC_CASE)
 #undef FC_CASE
     if (rc != FC_OK || gx_parts == 1 || defer_gx_sum) return rc;
-    return sum_parts(gxp, gx, (size_t)d->N * d->I, p.gx_part_stride, gx_parts, stream);
+    return sum_parts(w.gxp, gx, (size_t)d->N * d->I, p.gx_part_stride, gx_parts, stream);
 }
-
 
 }  // namespace fc

@@ -3,7 +3,7 @@
 
 namespace fc {
 
-template int backward_data_impl_mode<true>(const float*, const float*, const float*, const fc_csr*, const float*, float*, void*,
-                                           size_t, const fc_dims*, bool, hipStream_t, bool);
+template int backward_data_impl_mode<true>(const float*, const float*, const float*, const fc_csr*, const float*, float*, const BwdPlan&,
+                                           const PairWorkspace&, const fc_dims*, Drive, hipStream_t, GxSum);
 
 }  // namespace fc

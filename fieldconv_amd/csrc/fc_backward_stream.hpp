@@ -126,6 +126,41 @@ inline StreamPlan plan_stream(const fc_dims* d, int halves, bool factored) {
     return p;
 }
 
+// The workspace of the streaming arrangement: the gather kernel's H records, the streaming kernel's gW partials [P][F][KP][IP] and gxt
+// slices, and the gxt wavefronts' filter fragments (16-byte aligned: the three sizes before them are).  Its size: a null run.
+struct StreamWorkspace { char* hrec; float2* gwp; float2* gxt; uint32_t* wst; };
+inline StreamWorkspace stream_workspace(Carver& c, const StreamPlan& p) {
+    return {c.take_packed<char>(p.hrec_bytes), c.take_packed<float2>(p.gwp_bytes), c.take_packed<float2>(p.gxt_bytes),
+            c.take_packed<uint32_t>(p.wst_bytes)};
+}
+
+// Which arrangement a backward call with these dims runs, resolved ONCE per entry point: its plan, its workspace carved from the caller's
+// buffer, and where the finishing launches find the gW partials.  status: FC_OK, FC_ERR_UNSUPPORTED, or FC_ERR_WORKSPACE when the buffer
+// is missing or shorter than the arrangement's whole layout (describe_backward asks without one).
+struct BackwardRoute {
+    int status;
+    bool streams;               // the streaming arrangement (stream, sw), else the kernel pair (pair, pw)
+    StreamPlan stream; StreamWorkspace sw;
+    BwdPlan pair; PairWorkspace pw;
+    PartialsLayout partials;
+};
+inline BackwardRoute backward_route(const fc_dims* d, Drive drive, void* ws, size_t ws_bytes) {
+    BackwardRoute r = {};
+    Carver c(ws);
+    const StreamPlan& s = r.stream = plan_stream(d, halves_of(d), drive == Drive::kRecords);
+    if ((r.streams = s.ok)) {       // partial (p, f, k = o*R + r, i) at ((p*F + f)*KP + k)*IP + i
+        r.sw = stream_workspace(c, s);
+        r.partials = {reinterpret_cast<const float*>(r.sw.gwp), (size_t)s.F * s.KP * s.IP, (size_t)s.IP, (size_t)s.KP * s.IP, (size_t)d->R * s.IP, false, s.P};
+    } else {                        // partial (p, f, k = r*O + o, i) at ((p*F + f)*KP + k)*IP + i; in the split modes k = dump_k(r, o)
+        const BwdPlan& p = r.pair = plan_backward(d, halves_of(d));
+        r.pw = pair_workspace(c, p);
+        r.partials = {reinterpret_cast<const float*>(r.pw.gwp), (size_t)p.F * p.KP * p.IP, (size_t)d->O * p.IP, (size_t)p.KP * p.IP, (size_t)p.IP, p.gd.split != 0, p.P};
+        if (!(drive == Drive::kRecords ? p.ok_factored : p.ok)) r.status = FC_ERR_UNSUPPORTED;
+    }
+    if (r.status == FC_OK && (!ws || ws_bytes < c.used)) r.status = FC_ERR_WORKSPACE;
+    return r;
+}
+
 inline StreamArgs make_stream_args(const fc_dims* d, const StreamPlan& p) {
     StreamArgs a;
     a.N = d->N; a.I = d->I; a.O = d->O; a.R = d->R; a.F = p.FS; a.B = d->B; a.KS = p.KS;

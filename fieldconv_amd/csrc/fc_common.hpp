@@ -27,6 +27,9 @@ constexpr bool kDevSwitches = true;
 inline const char* dev_env(const char*) { return nullptr; }
 constexpr bool kDevSwitches = false;
 #endif
+// switches that several functions ask about, read once: FC_FILTER2=0, the LDS-staged filter-gradient kernel; FC_SPLIT_FINISH=1, two finishing launches
+inline bool filter_staged() { static const bool on = [] { const char* e = dev_env("FC_FILTER2"); return e && atoi(e) == 0; }(); return on; }
+inline bool split_finish() { static const bool on = [] { const char* e = dev_env("FC_SPLIT_FINISH"); return e && atoi(e) != 0; }(); return on; }
 
 constexpr int kWave = 64;
 constexpr int kTile = 16;        // vertices per tile == MFMA N

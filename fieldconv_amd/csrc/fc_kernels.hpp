@@ -36,17 +36,19 @@ int forward_impl(const float* x, const float* sten, const fc_csr* g, const float
                  const fc_dims* d, int kind, void* ws, size_t ws_bytes, const fc_epilogue* epi, hipStream_t stream);
 size_t forward_workspace_bytes(const fc_dims* d, int kind);
 size_t backward_workspace_bytes(const fc_dims* d);
-// (defer_gx_sum: when tiles are shared -- edge parts, frequency groups -- the partial gx arrays stay in the workspace and the launch that
-//  finishes the pass adds them: backward_finish_params_impl's gx_deferred)
+// What a backward entry point is told about its pass; from these and the dims backward_route() (fc_backward_stream.hpp) picks the arrangement.
+enum class Drive { kDenseRows, kRecords };      // the launch reads dense stencil rows / factored records (the C ABI's `records`)
+inline Drive drive_of(int records) { return records ? Drive::kRecords : Drive::kDenseRows; }
+// kDeferred: the partial gx arrays of shared tiles, or the gxt slices, stay in the workspace and the finishing launch forms gx (DeferredGx)
+enum class GxSum { kInPass, kDeferred };
+enum class StreamStages { kGather, kStream, kWholePass };      // the gather kernel | the streaming kernel + gx (fc_backward_gather / _stream time them apart)
 int backward_data_impl(const float* x, const float* gy, const float* sten, const fc_csr* g, const float* wpk, float* gx,
-                       void* ws, size_t ws_bytes, const fc_dims* d, bool factored, hipStream_t stream, bool defer_gx_sum = false);
-// (factored: the launch is record-driven -- with plan_stream() the H-streaming arrangement has done the filter kernel's work inside
-//  backward_data_impl, and the partials lie k = o*R + r)
-int backward_filter_impl(const float* x, void* ws, size_t ws_bytes, const fc_dims* d, hipStream_t stream, bool factored = false);
-bool backward_streams(const fc_dims* d, bool factored);
+                       void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, hipStream_t stream, GxSum gx_sum);
+int backward_filter_impl(const float* x, void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, hipStream_t stream);
+bool backward_streams(const fc_dims* d, Drive drive);
 int backward_stream_impl(const float* x, const float* gy, const float* rec, const fc_csr* g, const float* wpk, float* gx, void* ws,
-                         size_t ws_bytes, const fc_dims* d, hipStream_t stream, int stages);
-int backward_finish_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, hipStream_t stream, bool factored = false);
+                         size_t ws_bytes, const fc_dims* d, hipStream_t stream, StreamStages stages);
+int backward_finish_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, hipStream_t stream);
 // records != 0: images for the record-driven entry points (fc_forward_factored / _geometric, fc_backward_fused)
 int pack_filter_impl(const float* w_eff, float* wpk_fwd, float* wpk_bwd, const fc_dims* d, int records, hipStream_t stream);
 int pack_filter_params_impl(const float* zonal, const float* sph, const float* phase, int ftype, float* wpk_fwd,
@@ -66,20 +68,24 @@ int forward_ring_impl(const float* x, const float* rec, const fc_csr* g, const f
 int filter_param_grads_impl(const float* gw_eff, const float* zonal, const float* sph, const float* phase, int ftype,
                             float* g_zonal, float* g_sph, float* g_phase, const fc_dims* d, hipStream_t stream);
 
-// reduction of the filter-gradient partials fused with the parameter-gradient chain (fc_pack.hip); *_finish_params_impl
-// pick the partial layout of their kernel family
-// (o0, i0, Ifull: the filter is the block [o0, o0 + O) x [i0, i0 + I) of parameter tensors with Ifull input channels; whole
-// layer: 0, 0, 0)
-// (ring_pairs: the partials' k index is dump_k(r, o) * so instead of r * sr + o * so)
-// (bias_partials / bias_nparts / g_bias: fc_filter_params' rider -- extra workgroups of the same launch sum the modReLU's bias-gradient
-//  partials, bit-identically to tangent_nonlin_gb_reduce_kernel; gx_parts ...: a second rider, the deferred sum of the backward data
-//  kernel's partial gx arrays -- gx_count complex numbers, gx_stride apart, fc_sum_parts_kernel's arithmetic)
-int reduce_param_grads_impl(const float* gwp, size_t sp, size_t sr, size_t sf, size_t so, bool ring_pairs, int P, float* gw_eff,
-                            const float* zonal, const float* sph, const float* phase, int ftype, float* g_zonal, float* g_sph,
-                            float* g_phase, const fc_dims* d, hipStream_t stream, int o0 = 0, int i0 = 0, int Ifull = 0,
-                            const float* bias_partials = nullptr, int bias_nparts = 0, float* g_bias = nullptr,
-                            const float* gx_parts = nullptr, float* gx = nullptr, size_t gx_count = 0, size_t gx_stride = 0, int gx_nparts = 0,
-                            const float* gx_x = nullptr);
+// reduction of the filter-gradient partials fused with the parameter-gradient chain (fc_pack.hip); backward_route() fills in the
+// partial layout of its kernel family.  Partial (p, r, f, o, i) lies at gwp[p*sp + r*sr + f*sf + o*so + i]; with ring_pairs the
+// (r, o) part is dump_k(r, o) * so instead.
+struct PartialsLayout { const float* gwp; size_t sp, sr, sf, so; bool ring_pairs; int P; };
+// the filter is the block [o0, o0 + O) x [i0, i0 + I) of parameter tensors with Ifull input channels; the default: the whole layer
+struct FilterBlock { int o0 = 0, i0 = 0, Ifull = 0; };
+// A rider of the finishing launch: extra workgroups complete gx, (N, I) complex numbers.  kSumParts: the sum of the data kernel's
+// `nparts` partial arrays, `stride` apart (fc_sum_parts_kernel's arithmetic; one part or no gx: nothing to add).  kFromSlices: from the
+// streaming kernel's gxt slices and x, band limit B, KS slices per frequency (fc_backward_gx_kernel's arithmetic).
+struct GxRider {
+    enum Kind { kNone, kSumParts, kFromSlices } kind = kNone;
+    float* gx = nullptr;
+    struct SumParts { const float* parts; size_t stride; int nparts; } sum = {};
+    struct FromSlices { const float* gxt; const float* x; int B, KS; } slices = {};
+};
+// (fc_filter_params' rider, bias_partials: more workgroups sum the modReLU's bias-gradient partials, as tangent_nonlin_gb_reduce_kernel does)
+int reduce_param_grads_impl(const PartialsLayout& partials, float* gw_eff, const fc_filter_params& fp, const FilterBlock& block,
+                            const GxRider& gx_rider, const fc_dims* d, hipStream_t stream);
 // the rider as a launch of its own (fc_pointwise.hip): g_bias[c] = fixed-order sum over p of partials[p][c]
 int bias_partials_reduce_impl(const float* partials, int nparts, int C, float* g_bias, hipStream_t stream);
 
@@ -89,9 +95,10 @@ int bias_partials_reduce_impl(const float* partials, int nparts, int C, float* g
 __host__ __device__ inline int dump_k(int r, int o, int R, int O, bool pairs) {
     return (pairs && (r | 1) < R) ? (r >> 1) * 2 * O + 2 * o + (r & 1) : r * O + o;
 }
-int backward_finish_params_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, const fc_filter_params* fp, hipStream_t stream,
-                                int o0 = 0, int i0 = 0, int Ifull = 0,
-                                float* gx_deferred = nullptr, bool factored = false, const float* x_for_gx = nullptr);
+// what backward_data_impl left unfinished under GxSum::kDeferred: where gx goes, and x (the streaming arrangement's gx needs it)
+struct DeferredGx { float* gx = nullptr; const float* x = nullptr; };
+int backward_finish_params_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, const fc_filter_params& fp,
+                                const FilterBlock& block, const DeferredGx& deferred, hipStream_t stream);
 int pack_filter_block_impl(const float* w_eff, float* wpk_fwd, float* wpk_bwd, const fc_dims* d, int records, int o0, int i0, int Ifull,
                            hipStream_t stream);
 int pack_filter_params_block_impl(const float* zonal, const float* sph, const float* phase, int ftype, float* wpk_fwd, float* wpk_bwd,
@@ -126,6 +133,12 @@ inline bool allow_full_lds(const void* fn, size_t lds_bytes, bool (&done)[kMaxDe
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds) != hipSuccess) return false;
     if (dev >= 0 && dev < kMaxDevices) done[dev] = true;
     return true;
+}
+template <typename K, typename... A>
+int launch_full_lds(K kern, bool (&done)[kMaxDevices], dim3 grid, size_t lds_bytes, hipStream_t stream, A... args) {
+    if (!allow_full_lds(reinterpret_cast<const void*>(kern), lds_bytes, done)) return FC_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, grid, dim3(1024), lds_bytes, stream, args...);
+    return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 // LDS budget of the factored kernels in the current MFMA mode (the dense kernels need less)
 bool forward_fits(const fc_dims* d);

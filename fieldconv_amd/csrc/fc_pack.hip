@@ -464,27 +464,28 @@ __global__ __launch_bounds__(kRpThreads) void fc_reduce_param_grads_kernel(
     }
 }
 
-// gwp: the partials, P of them, entry (p, r, f, o, i) at gwp[p*sp + r*sr + f*sf + o*so + i]
-int reduce_param_grads_impl(const float* gwp, size_t sp, size_t sr, size_t sf, size_t so, bool ring_pairs, int P, float* gw_eff,
-                            const float* zonal, const float* sph, const float* phase, int ftype, float* g_zonal, float* g_sph,
-                            float* g_phase, const fc_dims* d, hipStream_t stream, int o0, int i0, int Ifull, const float* bias_partials,
-                            int bias_nparts, float* g_bias, const float* gx_parts, float* gx, size_t gx_count, size_t gx_stride, int gx_nparts,
-                            const float* gx_x) {
+int reduce_param_grads_impl(const PartialsLayout& pl, float* gw_eff, const fc_filter_params& fp, const FilterBlock& block,
+                            const GxRider& rider, const fc_dims* d, hipStream_t stream) {
     if (d->R > 8 || d->B > kMaxB || kRpPairs * d->R > kRpThreads) return FC_ERR_UNSUPPORTED;
     const int nit = (d->I + kRpPairs - 1) / kRpPairs;
-    const RpStrides st{sp, sr, sf, so, ring_pairs ? 1 : 0};
+    const RpStrides st{pl.sp, pl.sr, pl.sf, pl.so, pl.ring_pairs ? 1 : 0};
     const int main_blocks = d->O * nit;
     static const int dbg = [] { const char* e = dev_env("FC_DEBUG_RP"); return e ? atoi(e) : 0; }();      // development: 1 no partial loads, 2 no parameter chain
-    const int bias_blocks = (bias_partials && bias_nparts > 0 && g_bias) ? (d->O + kRpThreads / 64 - 1) / (kRpThreads / 64) : 0;
-    const bool sum_gx = gx_parts && gx && gx_nparts > 1;
-    const bool from_slices = gx_parts && gx && gx_x && gx_nparts < 0;      // (gx_nparts = -band limit: gx from the gxt slices, one complex number per thread)
-    const size_t gx_floats = gx_count * 2, gx_count4 = from_slices ? gx_count : sum_gx ? (gx_floats + 3) / 4 : 0;
+    const int bias_blocks = (fp.bias_partials && fp.bias_nparts > 0 && fp.g_bias) ? (d->O + kRpThreads / 64 - 1) / (kRpThreads / 64) : 0;
+    // the kernel tells its gx riders apart by the sign of one integer, formed here alone: n > 1 arrays to add, or -(B + 4 * (KS - 1))
+    const auto& sum = rider.sum;
+    const auto& sl = rider.slices;
+    const bool from_slices = rider.kind == GxRider::kFromSlices && sl.gxt && rider.gx && sl.x;      // one complex number per thread
+    const bool sum_gx = rider.kind == GxRider::kSumParts && sum.parts && rider.gx && sum.nparts > 1;
+    const int gx_nparts = rider.kind == GxRider::kFromSlices ? -(sl.B + 4 * (sl.KS - 1)) : sum.nparts;
+    const size_t gx_count = (size_t)d->N * d->I, gx_floats = gx_count * 2, gx_count4 = from_slices ? gx_count : sum_gx ? (gx_floats + 3) / 4 : 0;
     const int gx_blocks = (int)((gx_count4 + kRpThreads - 1) / kRpThreads);
     hipLaunchKernelGGL(fc_reduce_param_grads_kernel, dim3(main_blocks + bias_blocks + gx_blocks), dim3(kRpThreads), 0, stream,
-                       reinterpret_cast<const float2*>(gwp), st, P, reinterpret_cast<float2*>(gw_eff), zonal, sph, phase, ftype, g_zonal, g_sph,
-                       g_phase, d->O, d->I, d->R, d->B, o0, i0, Ifull > 0 ? Ifull : d->I, bias_partials, bias_nparts, g_bias, main_blocks,
-                       reinterpret_cast<const f32x4*>(gx_parts), reinterpret_cast<f32x4*>(gx), gx_count4, gx_stride / 2, gx_nparts,
-                       gx_floats % 4, main_blocks + bias_blocks, reinterpret_cast<const float2*>(gx_x), dbg);
+                       reinterpret_cast<const float2*>(pl.gwp), st, pl.P, reinterpret_cast<float2*>(gw_eff), fp.zonal, fp.spherical, fp.phase,
+                       fp.ftype, fp.g_zonal, fp.g_spherical, fp.g_phase, d->O, d->I, d->R, d->B, block.o0, block.i0,
+                       block.Ifull > 0 ? block.Ifull : d->I, fp.bias_partials, fp.bias_nparts, fp.g_bias, main_blocks,
+                       reinterpret_cast<const f32x4*>(rider.kind == GxRider::kFromSlices ? sl.gxt : sum.parts), reinterpret_cast<f32x4*>(rider.gx),
+                       gx_count4, sum.stride / 2, gx_nparts, gx_floats % 4, main_blocks + bias_blocks, reinterpret_cast<const float2*>(sl.x), dbg);
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 

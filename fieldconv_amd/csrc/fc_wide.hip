@@ -145,6 +145,7 @@ int fc_backward_wide(const float* x, const float* gy, const float* sten_or_rec_s
     const fc::WideBwdWs w = fc::wide_bwd_ws(ws, p);
     const int N = dims->N, I = dims->I, O = dims->O, blk = p.blk;
     const size_t bstride = (size_t)N * blk * 2;              // floats between the x / gy blocks
+    const fc::Drive drive = fc::drive_of(records);
     for (int ib = 0; ib < p.nib; ++ib) {
         const int bi = (I - ib * blk) < blk ? (I - ib * blk) : blk;
         const int rc = fc::copy_block(w.xb + ib * bstride, bi, x + 2 * (size_t)ib * blk, I, N, bi, st);
@@ -167,19 +168,19 @@ int fc_backward_wide(const float* x, const float* gy, const float* sten_or_rec_s
                             : fc::pack_filter_block_impl(w_eff, nullptr, w.wpk, &d, records, ob * blk, ib * blk, I, st);
             if (rc != FC_OK) return rc;
             float* part = p.nob == 1 ? w.gxb : w.parts + ob * w.pstride;
-            rc = fc::backward_data_impl(w.xb + ib * bstride, w.gyb + ob * bstride, sten_or_rec_s, by_source, w.wpk, part, w.cws, w.cws_bytes, &d, records != 0,
-                                        st);
+            rc = fc::backward_data_impl(w.xb + ib * bstride, w.gyb + ob * bstride, sten_or_rec_s, by_source, w.wpk, part, w.cws, w.cws_bytes, &d, drive, st,
+                                        fc::GxSum::kInPass);
             if (rc != FC_OK) return rc;
-            rc = fc::backward_filter_impl(w.xb + ib * bstride, w.cws, w.cws_bytes, &d, st, records != 0);
+            rc = fc::backward_filter_impl(w.xb + ib * bstride, w.cws, w.cws_bytes, &d, drive, st);
             if (rc != FC_OK) return rc;
             if (params) {
                 fc_filter_params block_params = *params;             // (the bias rider belongs to the whole layer: after the blocks)
                 block_params.bias_partials = nullptr;
                 block_params.bias_nparts = 0;
                 block_params.g_bias = nullptr;
-                rc = fc::backward_finish_params_impl(w.gwb, w.cws, w.cws_bytes, &d, &block_params, st, ob * blk, ib * blk, I, nullptr, records != 0);
+                rc = fc::backward_finish_params_impl(w.gwb, w.cws, w.cws_bytes, &d, drive, block_params, fc::FilterBlock{ob * blk, ib * blk, I}, fc::DeferredGx{}, st);
             } else {            // explicit filter: the block's gradient goes into its block of gw_eff (rows o, bi*R*F numbers each)
-                rc = fc::backward_finish_impl(w.gwb, w.cws, w.cws_bytes, &d, st, records != 0);
+                rc = fc::backward_finish_impl(w.gwb, w.cws, w.cws_bytes, &d, drive, st);
                 const int rf = dims->R * (2 * dims->B + 1);
                 if (rc == FC_OK)
                     rc = fc::copy_block(gw_eff + 2 * (((size_t)ob * blk * I + (size_t)ib * blk) * rf), I * rf, w.gwb, bi * rf, bo, bi * rf, st);

@@ -16,9 +16,14 @@ struct Carver {
     // room: where wanted, the bytes the piece occupies (for a piece that is handed on as another entry point's workspace)
     template <typename T = void>
     T* take(size_t bytes, size_t* room = nullptr) {
-        T* r = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += align256(bytes);
         if (room) *room = align256(bytes);
+        return take_packed<T>(align256(bytes));
+    }
+    // no rounding: the convolution's backward workspaces are older than the 256-byte rule, and their pieces stay back to back
+    template <typename T = void>
+    T* take_packed(size_t bytes) {
+        T* r = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += bytes;
         return r;
     }
 };

@@ -19,7 +19,12 @@ if ROOT not in sys.path:
 NS = (1, 63, 64, 65, 300, 1024, 20000)         # the edges of the per-vertex rules: one chunk, around 64 rows, several workgroups
 PARTS = (0, 1, 2)
 TOPK = (1, 2, 4, 5, 8)
-FAKE = 0x10000                                  # a non-null address: the queries test pointers, they never follow these
+CONV_NS = (1, 16, 17, 777, 3071, 3072, 4096, 8192, 20000, 170003)
+# (I, O, R, B): the channel pairs (1,1) (16,16) (40,48) (48,48) (64,64) (64,48) against the ring / band-limit pairs (2,1) (6,1) (6,2) (6,3)
+# (8,3) (5,2), paired so that the reference's default layer (48, 48, 6, 2) is among them; CONV_SHAPES_2: the same lists paired one further
+CONV_SHAPES = ((1, 1, 5, 2), (16, 16, 2, 1), (40, 48, 6, 1), (48, 48, 6, 2), (64, 64, 6, 3), (64, 48, 8, 3))
+CONV_SHAPES_2 = ((1, 1, 2, 1), (16, 16, 6, 1), (40, 48, 6, 2), (48, 48, 6, 3), (64, 64, 8, 3), (64, 48, 5, 2))
+FAKE = 0x10000                                 # a non-null address: the queries test pointers, they never follow these
 
 
 def rows(lib=None):
@@ -111,6 +116,35 @@ def rows(lib=None):
                     for bwd in (0, 1):
                         q('fc_wide_workspace_bytes', ctypes.byref(d), block, records, bwd,
                           show=('N=%d E=%d I=%d O=%d R=6 B=2' % (N, 12 * N, I, O), block, records, bwd))
+
+    # the convolution's own buffers.  Backward: the larger of the pair arrangement (hdump | gwp | gxp) and the streaming one
+    # (hrec | gwp | gxt | wst), in each arithmetic mode.  3071 / 3072 vertices sit on the streaming threshold of 256 CUs, 170003 takes
+    # the H records past 4 GiB, 40 neighbours at 777 vertices switch the edge split on.
+    def conv_rows(N, E, shapes, packed):
+        for I, O, R, B in shapes:
+            shape = 'N=%d E=%d I=%d O=%d R=%d B=%d' % (N, E, I, O, R, B)
+            for mode in (0, 1, 2):
+                d = FcDims(N, E, I, O, R, B, mode=mode)
+                q('fc_backward_workspace_bytes', ctypes.byref(d), 1, show=(shape + ' mode=%d' % mode, 1))
+            d = FcDims(N, E, I, O, R, B, mode=0)
+            q('fc_backward_workspace_bytes', ctypes.byref(d), 0, show=(shape, 0))
+            q('fc_backward_streams', ctypes.byref(d), 1, show=(shape, 1))
+            q('fc_forward_workspace_bytes', ctypes.byref(d), show=(shape,))
+            for records in (0, 1) if packed else ():
+                q('fc_packed_filter_floats_fwd', ctypes.byref(d), records, show=(shape, records))
+                q('fc_packed_filter_floats_bwd', ctypes.byref(d), records, show=(shape, records))
+
+    for N in CONV_NS:
+        conv_rows(N, 12 * N, CONV_SHAPES, N in (16, 777, 3072, 20000))
+        for O in (1, 16, 48, 64):
+            q('fc_tangent_nonlin_backward_workspace_bytes', N, O)
+        q('fc_tangent_nonlin_backward_groups', N)
+    conv_rows(777, 40 * 777, CONV_SHAPES, False)
+    conv_rows(3072, 12 * 3072, CONV_SHAPES_2, False)
+    d = FcDims(3072, 12 * 3072, 48, 48, 6, 2, mode=0)
+    q('fc_backward_streams', ctypes.byref(d), 0, show=('N=3072 E=36864 I=48 O=48 R=6 B=2', 0))
+    for factored in (0, 1):
+        q('fc_records_flags', ctypes.byref(d), factored, show=('N=3072 E=36864 I=48 O=48 R=6 B=2', factored))
     return out
 
 
