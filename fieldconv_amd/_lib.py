@@ -68,6 +68,12 @@ class FcLiftBlockParams(ctypes.Structure):
                 ('bias', _vp), ('g_zonal_ang', _vp), ('g_zonal_mag', _vp), ('g_phase', _vp), ('g_bias', _vp)]
 
 
+class FcAdamCtl(ctypes.Structure):
+    """fc_adam_ctl: the hyper-parameters and controls of fc_adam_step_ctl, read on the host at call time"""
+    _fields_ = [('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('weight_decay', ctypes.c_float),
+                ('decoupled', _c_int32), ('max_norm', ctypes.c_float), ('skip_nonfinite', _c_int32), ('ema_decay', ctypes.c_float)]
+
+
 _DP = ctypes.POINTER(FcDims)
 _MP = ctypes.POINTER(FcMesh)
 _RBP = ctypes.POINTER(FcResnetBlockParams)
@@ -126,6 +132,8 @@ SIGNATURES = {
     'fc_echo_forward': (ctypes.c_int, [_vp, _vp, _vp, _CP, _vp, _vp, _c_int32, _c_int32, _c_int32, _c_int32, _vp]),
     'fc_echo_backward': (ctypes.c_int, [_vp, _vp, _vp, _CP, _vp, _vp, _vp, _vp, _c_int32, _c_int32, _c_int32, _c_int32, _vp]),
     'fc_adam_step': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz] + [ctypes.c_float] * 5 + [_vp]),
+    'fc_adam_ctl_workspace_bytes': (_sz, [_sz]),
+    'fc_adam_step_ctl': (ctypes.c_int, [_vp] * 9 + [_sz, _sz, ctypes.POINTER(FcAdamCtl), _vp]),
     'fc_precomp_workspace_bytes': (_sz, [_c_int32, _c_int32]),
     'fc_precomp_mark': (ctypes.c_int, [_vp, _vp, ctypes.c_float, _c_int32, _c_int32, _vp, _sz, _vp]),
     'fc_precomp_graph': (ctypes.c_int, [_vp] * 5 + [ctypes.c_float] + [_c_int32] * 7 + [_vp] * 16 + [_vp, _sz, _vp, _sz, _vp]),

@@ -558,6 +558,52 @@ int fc_precomp_graph(const float* log_mag, const float* log_ang, const float* xp
 int fc_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step, size_t n, float lr,
                  float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ---- the same step with controls a captured step can steer from the device (csrc/fc_optim.hip) ------------------------- *
+ * The buffers are those above; in addition
+ *   lr      one DEVICE float: the learning rate, read by the update kernel (a replayed graph follows what is written there)
+ *   stats   four DEVICE floats, written every call: {gradient norm before clipping, clip coefficient, 1 if this step was
+ *           skipped else 0, number of steps skipped so far (stats[3] is read and incremented: zero it once)}
+ *   ema     n floats, the moving average of the parameters; NULL unless ema_decay >= 0
+ *   ctl     the struct below, read on the host at call time (so its values are constants of a captured graph)
+ * Three launches (two when neither the norm nor the skip is wanted), no atomics, no host synchronisation:
+ *  a. sum of squares, launched when max_norm > 0 or skip_nonfinite: workgroup b of 256 threads covers the float4
+ *     [1024 b, 1024 (b+1)) of grads; thread t adds, to a running DOUBLE that starts at 0, ((x^2 + y^2) + z^2) + w^2 of the float4
+ *     1024 b + 256 r + t for r = 0, 1, 2, 3 in that order (every square formed in double: exact); the 64 lanes of a wavefront
+ *     are combined by an xor butterfly (lane distance 32, 16, 8, 4, 2, 1), then the workgroup's four wavefronts are added in
+ *     index order starting from 0, and the result is partial[b].  There are ceil(n / 4096) partials.
+ *  b. finalize and tick, one workgroup of 256 threads: thread t adds partial[t], partial[t + 256], ... in that order to a
+ *     double that starts at 0, then butterfly and wavefront order as in a.: S.  The order of every addition is a function of n
+ *     alone, so two runs give the same bits.  A NaN or an infinity anywhere in grads makes S non-finite; S cannot overflow
+ *     otherwise.  Then, with norm_d = sqrt(S) in double:
+ *         skip  = skip_nonfinite && !isfinite(S)
+ *         coef  = max_norm > 0 ? (float)min(1, (double)max_norm / (norm_d + 1e-6)) : 1        (torch's clip_grad_norm_, in double,
+ *                 rounded once; as in torch's clamp a NaN quotient stays a NaN)
+ *         step[0] += 1 unless skip;  stats = {(float)norm_d, coef, skip, stats[3] + skip}
+ *     (float)norm_d may be inf while S is finite: that is reported, not a skip.  When neither the norm nor the skip is wanted the
+ *     launch only ticks and writes stats = {0, 1, 0, stats[3]}.
+ *  c. update, one pass over the flat buffers.  If skip, nothing is written: params, the moments, ema and step keep their bits.
+ *     Otherwise, with t = step[0] and lr = lr[0]:
+ *         g  = coef * grads[i]                       (grads itself is NOT modified, unlike torch's clip_grad_norm_)
+ *         decoupled == 0:  g' = g + wd p             (L2, as the step above)
+ *         decoupled != 0:  p = p * (1 - lr * wd) first, then g' = g          (torch.optim.AdamW's order)
+ *         m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ *         ema_decay >= 0:  ema = d * ema + (1 - d) * p      (the new p; d = ema_decay < 1)
+ *     every operation in float32.  With max_norm <= 0, skip_nonfinite == 0, decoupled == 0 and ema_decay < 0 the results are the
+ *     bits of the step above for the same lr.
+ * Errors as above (null pointers, n not a multiple of 4, ema missing or ema_decay >= 1: FC_ERR_BAD_ARGUMENT); n == 0 is FC_OK and
+ * launches nothing.  Workspace: the query below, 256 + 8 ceil(n / 4096) bytes rounded up to 256; FC_ERR_WORKSPACE when it is missing
+ * or smaller.  It carries coef and skip from b. to c. and need not be kept between calls. */
+typedef struct fc_adam_ctl {
+    float beta1, beta2, eps, weight_decay;
+    int32_t decoupled;        /* 0: L2 weight decay, else decoupled (AdamW) */
+    float max_norm;           /* <= 0: no clipping */
+    int32_t skip_nonfinite;   /* != 0: a step whose gradient holds a NaN or an infinity changes nothing */
+    float ema_decay;          /* < 0: no moving average */
+} fc_adam_ctl;
+size_t fc_adam_ctl_workspace_bytes(size_t n);
+int fc_adam_step_ctl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, float* step, const float* lr,
+                     float* stats, void* workspace, size_t workspace_bytes, size_t n, const fc_adam_ctl* ctl, void* stream);
+
 /* ---- support graph (the reference's SupportGraph transform: farthest-point sampling, then a radius search) ---------- *
  * Distances: d2 = (dx*dx + dy*dy) + dz*dz in fp32 with dx = p_n.x - p_q.x, every operation rounded on its own (no fused
  * multiply-add), in both searches.  pos: (N,3) float32, contiguous, device memory.
