@@ -63,7 +63,7 @@ int fc_supported(const fc_dims* dims) { return fc::dims_supported(dims) ? 1 : 0;
 int fc_describe_kernels(const fc_dims* dims, int32_t kind, char* buffer, size_t buffer_bytes) {
     if (!buffer || buffer_bytes < 2 || kind < 0 || kind > 2 || !fc::dims_valid(dims)) return FC_ERR_BAD_ARGUMENT;
     if (!fc::dims_supported(dims)) return FC_ERR_UNSUPPORTED;
-    char fwd[256], bwd[768];
+    char fwd[320], bwd[768];
     fc::describe_forward(dims, kind, fwd, sizeof(fwd));
     fc::describe_backward(dims, kind != 0, bwd, sizeof(bwd));
     snprintf(buffer, buffer_bytes, "%s; %s", fwd, bwd);

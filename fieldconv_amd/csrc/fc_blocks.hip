@@ -90,9 +90,7 @@ static int conv_forward(const float* x, const fc_mesh* m, const fc_dims* d, cons
         const int rc = pack_filter_params_impl(f.zonal, f.spherical, f.phase, f.ftype, wpk_f, wpk_b, d, records, st);
         if (rc != FC_OK) return rc;
     }
-    const size_t need = records ? forward_workspace_bytes(d, m->kind) : 0;
-    const bool give = need != 0 && need <= ws_bytes;
-    return forward_impl(x, m->fwd, m->by_target, wpk_f, y, d, m->kind, give ? ws : nullptr, give ? need : 0, epi, st);
+    return forward_impl(x, m->fwd, m->by_target, wpk_f, y, d, m->kind, ws, ws_bytes, epi, st);
 }
 
 }  // namespace fc

@@ -514,60 +514,4 @@ static int launch_forward(const float2* x, const float* sten, const fc_csr* g, c
     return hipGetLastError() == hipSuccess ? FC_OK : FC_ERR_LAUNCH;
 }
 
-// Edge split for small meshes: how many workgroups share a tile (log2).  Only when the tiles alone leave CUs idle and
-// every part still gets a few slots per target.
-inline int forward_parts_log2(const fc_dims* d, int kind) { return kind == 0 ? 0 : edge_parts_log2(d); }
-inline size_t forward_part_stride(const fc_dims* d) { return part_stride((size_t)d->N * d->O); }
-inline size_t forward_workspace_bytes_impl(const fc_dims* d, int kind) {
-    const int pl = forward_parts_log2(d, kind);
-    return pl ? (forward_part_stride(d) << pl) * sizeof(float2) : 0;
-}
-
-template <bool SPLIT>
-int forward_impl_mode(const float* x, const float* sten, const fc_csr* g, const float* wpk, float* y,
-                      const fc_dims* d, int kind, void* ws, size_t ws_bytes, const fc_epilogue* epi, hipStream_t stream) {
-    const bool factored = kind != 0;
-    FwdArgs a;
-    a.N = d->N; a.I = d->I; a.O = d->O;
-    a.g = make_mma_geom(d->O, d->R, d->I, SPLIT ? halves_of(d) : 0);
-    a.ntiles = (d->N + kTile - 1) / kTile;
-    // without a workspace the tiles are not split (same result, fewer workgroups)
-    a.parts_log2 = (ws && ws_bytes >= forward_workspace_bytes_impl(d, kind)) ? forward_parts_log2(d, kind) : 0;
-    a.part_stride = (uint32_t)forward_part_stride(d);
-    a.epi = make_epi(epi);
-    a.wpk_bytes = (uint32_t)(packed_image_floats(d->O, d->R, d->I, 2 * d->B + 1, a.g.split) * sizeof(float));
-    static const int dbg = [] { const char* e = dev_env("FC_DEBUG"); return e ? atoi(e) : 0; }();       // read once per process
-    a.dbg = dbg;
-    a.ring_chunks = factored ? kRingChunks : 0;
-    const size_t ring = (size_t)kWaves * a.ring_chunks * 1024;
-    // dense: one tile per workgroup; factored: persistent (the record ring is primed one tile ahead)
-    const int nvt = a.ntiles << a.parts_log2;
-    const int grid = factored ? (nvt < num_cus() ? nvt : num_cus()) : a.ntiles;
-    const TileItems items = tile_items(a.ntiles, factored ? grid : 0, a.parts_log2);
-    a.nv_full = items.nv_full;
-    a.nv_total = items.nv_total;
-    // With two slab buffers the epilogue parks its fp32 k-partials in the idle one.  A workgroup that walks several
-    // tiles would then read those bits back as halves in the k padding [R*KI, KP) of the next tile's slab rows (the
-    // padding is zeroed once, before the tile loop), and 0 x NaN poisons the accumulators: shapes with k padding
-    // keep the partials in their own region whenever a workgroup sees more than one tile.
-    const bool aliasing_hazard = a.g.KP > d->R * a.g.KI && grid < a.nv_total;
-    a.slabs = (SPLIT && !aliasing_hazard && partial_floats(a.g.NKP, a.g.MP) <= slab_floats(a.g) &&
-               forward_lds_floats(a.g, 2) * sizeof(float) + ring <= kMaxLds) ? 2 : 1;
-    const size_t lds = forward_lds_floats(a.g, a.slabs) * sizeof(float) + ring;
-    if (lds > kMaxLds) return FC_ERR_UNSUPPORTED;
-    int rc = FC_ERR_UNSUPPORTED;
-#define FC_CASE(RR, BB)                                                                                              \
-    if (d->R == RR && d->B == BB) {                                                                                  \
-        const float2* x2 = reinterpret_cast<const float2*>(x);                                                       \
-        float2* y2 = reinterpret_cast<float2*>(a.parts_log2 ? static_cast<float*>(ws) : y);                          \
-        if (kind == 2) rc = launch_forward<RR, BB, 2, SPLIT>(x2, sten, g, wpk, y2, a, lds, grid, stream);            \
-        else if (kind == 1) rc = launch_forward<RR, BB, 1, SPLIT>(x2, sten, g, wpk, y2, a, lds, grid, stream);       \
-        else rc = launch_forward<RR, BB, 0, SPLIT>(x2, sten, g, wpk, y2, a, lds, grid, stream);                      \
-    }
-    FC_FOR_EACH_SHAPE(FC_CASE)
-#undef FC_CASE
-    if (rc != FC_OK || a.parts_log2 == 0) return rc;
-    return sum_parts_epilogue(static_cast<const float*>(ws), y, (size_t)d->N * d->O, a.part_stride, 1 << a.parts_log2, d->O, a.epi, stream);
-}
-
 }  // namespace fc

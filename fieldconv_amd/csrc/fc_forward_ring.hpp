@@ -65,6 +65,11 @@ __host__ __device__ inline MmaGeom ring_geom(int M, int F, int channels, int hal
     if (g.NKP < 1) g.NKP = 1;
     return g;
 }
+// Floats of the ring-major filter image: MP inverse row scales, then for each of the R rings 2 * halves planes of MP x KP halves
+inline size_t packed_ring_image_floats(int M, int F, int channels, int R, int halves) {
+    const MmaGeom g = ring_geom(M, F, channels, halves);
+    return (size_t)g.MP + (size_t)R * halves * g.MP * g.KP;
+}
 
 // Work item of workgroup `b`'s first (with spread_cus: only) pass.
 __device__ __forceinline__ int ring_item(const RingArgs& a) {

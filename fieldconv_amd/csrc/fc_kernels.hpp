@@ -31,7 +31,8 @@ inline int num_cus() {
 constexpr int kMaxChannels = 64;     // one channel per lane in the gather phases
 
 // kind: 0 dense stencil rows, 1 factored records, 2 geometric-phase records
-// ws: optional scratch of forward_workspace_bytes(d, kind) bytes that lets several workgroups share a tile on small meshes
+// ws: optional scratch of forward_workspace_bytes(d, kind) bytes that lets several workgroups share a tile on small meshes; the callers
+// hand over what they have: a missing or short one runs the unsplit launch (same result)
 int forward_impl(const float* x, const float* sten, const fc_csr* g, const float* wpk, float* y,
                  const fc_dims* d, int kind, void* ws, size_t ws_bytes, const fc_epilogue* epi, hipStream_t stream);
 size_t forward_workspace_bytes(const fc_dims* d, int kind);
@@ -49,7 +50,7 @@ bool backward_streams(const fc_dims* d, Drive drive);
 int backward_stream_impl(const float* x, const float* gy, const float* rec, const fc_csr* g, const float* wpk, float* gx, void* ws,
                          size_t ws_bytes, const fc_dims* d, hipStream_t stream, StreamStages stages);
 int backward_finish_impl(float* gw_eff, void* ws, size_t ws_bytes, const fc_dims* d, Drive drive, hipStream_t stream);
-// records != 0: images for the record-driven entry points (fc_forward_factored / _geometric, fc_backward_fused)
+// records != 0: images for the record-driven entry points (fc_forward_factored / _geometric, fc_backward_all and the staged backward calls)
 int pack_filter_impl(const float* w_eff, float* wpk_fwd, float* wpk_bwd, const fc_dims* d, int records, hipStream_t stream);
 int pack_filter_params_impl(const float* zonal, const float* sph, const float* phase, int ftype, float* wpk_fwd,
                             float* wpk_bwd, const fc_dims* d, int records, hipStream_t stream);
@@ -59,12 +60,6 @@ int pack_filter_params_pair_impl(const fc_filter_params& f0, float* fwd0, float*
 size_t packed_filter_floats_fwd(const fc_dims* d, int records);
 size_t packed_filter_floats_bwd(const fc_dims* d, int records);
 
-// ring-major record kernels (fc_forward_ring.hpp)
-bool ring_enabled(const fc_dims* d);
-bool forward_ring_fits(const fc_dims* d);
-size_t packed_ring_image_floats(int M, int F, int channels, int R, int halves);
-int forward_ring_impl(const float* x, const float* rec, const fc_csr* g, const float* wpk, float* y, const fc_dims* d, int kind,
-                      void* ws, size_t ws_bytes, const fc_epilogue* epi, hipStream_t stream);
 int filter_param_grads_impl(const float* gw_eff, const float* zonal, const float* sph, const float* phase, int ftype,
                             float* g_zonal, float* g_sph, float* g_phase, const fc_dims* d, hipStream_t stream);
 

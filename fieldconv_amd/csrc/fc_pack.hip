@@ -9,7 +9,7 @@
 #include "fc_common.hpp"
 #include "fc_kernels.hpp"
 #include "fc_tile.hpp"
-#include "fc_forward_ring.hpp"
+#include "fc_forward_route.hpp"
 
 namespace fc {
 
@@ -195,12 +195,8 @@ static unsigned pack_blocks(const MmaGeom& g, int F) {      // F: slabs of plane
     return g.split ? (unsigned)(g.MP * F) : (unsigned)(((size_t)F * 2 * g.MP * g.KP + kPackThreads - 1) / kPackThreads);
 }
 
-static bool ring_forward_image(const fc_dims* d, int records) { return (records & 1) && forward_ring_fits(d); }
-
-size_t packed_filter_floats_fwd(const fc_dims* d, int records) {
-    if (ring_forward_image(d, records)) return packed_ring_image_floats(d->O, 2 * d->B + 1, d->I, d->R, halves_of(d));
-    return packed_image_floats(d->O, d->R, d->I, 2 * d->B + 1, halves_of(d));
-}
+// (the forward image's size and layout are the route's: the launch must be given the same dims and records, fc_forward_route.hpp)
+size_t packed_filter_floats_fwd(const fc_dims* d, int records) { return forward_route(d, records & 1, num_cus()).image_floats; }
 size_t packed_filter_floats_bwd(const fc_dims* d, int records) {
     (void)records;
     return packed_image_floats(d->I, d->R, d->O, 2 * d->B + 1, halves_of(d));
@@ -210,8 +206,9 @@ size_t packed_filter_floats_bwd(const fc_dims* d, int records) {
 static unsigned pack_args(PackArgs& a, int ftype, bool want_fwd, bool want_bwd, const fc_dims* d, int records, int o0, int i0, int Ifull) {
     a.O = d->O; a.I = d->I; a.R = d->R; a.B = d->B; a.F = 2 * d->B + 1; a.ftype = ftype;
     a.o0 = o0; a.i0 = i0; a.Ifull = Ifull > 0 ? Ifull : d->I;
-    a.ring_f = ring_forward_image(d, records & 1) ? 1 : 0;
-    a.gf = a.ring_f ? ring_geom(d->O, a.F, d->I, halves_of(d)) : make_mma_geom(d->O, d->R, d->I, halves_of(d));
+    const ForwardRoute r = forward_route(d, records & 1, num_cus());
+    a.ring_f = r.ring_image ? 1 : 0;
+    a.gf = r.g;
     a.gb = make_mma_geom(d->I, d->R, d->O, halves_of(d));
     a.blocks_f = want_fwd ? pack_blocks(a.gf, a.ring_f ? a.R : a.F) : 0u;                // no forward image wanted: backward image only
     const unsigned blocks_b = pack_blocks(a.gb, a.F);

@@ -404,6 +404,46 @@ inline TileItems tile_items(int ntiles, int grid, int parts_log2) {
     }
     return t;
 }
+// How a forward launch walks the mesh: dense stencil rows (one workgroup per tile), per-edge records with one 16-wavefront workgroup per
+// CU (frequency-major, fc_forward_kernels.hpp), or records with two 8-wavefront workgroups per CU (ring-major, fc_forward_ring.hpp).
+enum class Arrangement { kDenseRows, kFrequencyMajor, kRingMajor };
+// The work items of a forward launch and its grid -- the one place that says what the schedule is.
+//   dense rows        one workgroup per tile, whole tiles only
+//   frequency-major   persistent, a workgroup per CU; the last round as half tiles by tile_items' rule
+//   ring-major        persistent, two workgroups per CU; without an edge split, and unless FC_RING_HALVES=0: the last round as half tiles
+//                     when those still fit one round, and between one and two workgroups per CU (a FAUST-sized mesh: 313 tiles on 256
+//                     CUs, where whole tiles would leave some CUs with two of them and the rest with one) as many half tiles as fill
+//                     every slot -- W whole + 2 (items - W) half tiles = 2 cus items, one per workgroup (RingArgs::spread_cus)
+struct TileSchedule {
+    int grid, nv_full, nv_total, spread_cus;
+};
+inline TileSchedule tile_schedule(int ntiles, int parts_log2, int cus, Arrangement arrangement) {
+    const int items = ntiles << parts_log2;
+    TileSchedule s = {ntiles, items, items, 0};
+    if (arrangement == Arrangement::kDenseRows) return s;
+    if (arrangement == Arrangement::kFrequencyMajor) {
+        s.grid = items < cus ? items : cus;
+        const TileItems t = tile_items(ntiles, s.grid, parts_log2);
+        s.nv_full = t.nv_full;
+        s.nv_total = t.nv_total;
+        return s;
+    }
+    s.grid = items < 2 * cus ? items : 2 * cus;
+    static const bool halves = !(dev_env("FC_RING_HALVES") && atoi(dev_env("FC_RING_HALVES")) == 0);
+    if (!halves || parts_log2 != 0 || s.grid <= 0) return s;
+    const int rem = items % s.grid;
+    if (rem > 0 && 2 * rem <= s.grid) {
+        s.nv_full = items - rem;
+        s.nv_total = s.nv_full + 2 * rem;
+    }
+    if (items > cus && items < 2 * cus) {
+        s.nv_full = 2 * items - 2 * cus;
+        s.nv_total = 2 * cus;
+        s.spread_cus = cus;
+        s.grid = 2 * cus;
+    }
+    return s;
+}
 // vertex of row `row` (0..15) of work item `item`, or N for a row without a vertex; parts_log2 != 0: items are
 // (tile << parts_log2) + part
 __host__ __device__ inline int item_vertex(int item, int row, int nv_full, int parts_log2, int N) {
@@ -414,14 +454,15 @@ __host__ __device__ inline int item_vertex(int item, int row, int nv_full, int p
 
 // How many workgroups share a tile of 16 vertices (log2): only when the tiles alone leave CUs idle and every part still
 // gets a few edges per vertex.  FC_EDGE_PARTS_MAX (development) caps it.
-inline int edge_parts_log2(const fc_dims* d) {
+inline int edge_parts_log2(const fc_dims* d, int cus) {
     if (d->N <= 0) return 0;
     const int ntiles = (d->N + kTile - 1) / kTile;
     const long deg = (long)d->E / d->N;
     static const int cap = [] { const char* e = dev_env("FC_EDGE_PARTS_MAX"); return e ? atoi(e) : 3; }();       // read once per process
     int pl = 0;
-    while (pl < cap && (ntiles << (pl + 1)) <= num_cus() && (deg >> (pl + 1)) >= 8) ++pl;
+    while (pl < cap && (ntiles << (pl + 1)) <= cus && (deg >> (pl + 1)) >= 8) ++pl;
     return pl;
 }
+inline int edge_parts_log2(const fc_dims* d) { return edge_parts_log2(d, num_cus()); }
 
 }  // namespace fc

@@ -118,9 +118,7 @@ int fc_forward_wide(const float* x, const float* sten_or_records, const fc_csr* 
                             : fc::pack_filter_block_impl(w_eff, w.wpk, nullptr, &d, records, ob * blk, ib * blk, I, st);
             if (rc != FC_OK) return rc;
             fc_epilogue epi = {ib > 0 ? w.yb : nullptr, nullptr, nullptr};      // the sum over the input blocks: y_block += this block's output
-            const size_t fws = records ? fc::forward_workspace_bytes(&d, kind) : 0;
-            rc = fc::forward_impl(w.xb + ib * xstride, sten_or_records, by_target, w.wpk, w.yb, &d, kind, fws && fws <= w.cws_bytes ? w.cws : nullptr,
-                                  fws && fws <= w.cws_bytes ? fws : 0, ib > 0 ? &epi : nullptr, st);
+            rc = fc::forward_impl(w.xb + ib * xstride, sten_or_records, by_target, w.wpk, w.yb, &d, kind, w.cws, w.cws_bytes, ib > 0 ? &epi : nullptr, st);
             if (rc != FC_OK) return rc;
         }
         const int rc = fc::copy_block(y + 2 * (size_t)ob * blk, O, w.yb, bo, N, bo, st);

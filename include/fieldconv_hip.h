@@ -80,7 +80,11 @@ int fc_supported(const fc_dims* dims);
 /* Which kernels a forward + backward pass with these dims launches in this process, as one line of text (kernel family,
  * record kind, MFMA mode, tile counts): the library picks them from the dims, the device's CU count, the MFMA mode and -- in the
  * development build only -- its switches, and a benchmark line should say what it timed.  kind: 0 dense rows, 1 factored
- * records, 2 geometric records in the forward pass (factored ones in the backward pass).  No GPU work. */
+ * records, 2 geometric records in the forward pass (factored ones in the backward pass).  No GPU work.
+ * The forward part ends with what the launch is, given its workspace: grid=G (workgroups) whole=W half=H (work items: 16-vertex tiles
+ * and 8-vertex half tiles; with the edge split a tile counts once per part) spread=0|1 (ring-major: one item per workgroup, whole and
+ * half tiles dealt so that every CU holds at most a whole and a half tile) lds=BYTES (dynamic LDS of a workgroup) cus=C (the CU count
+ * the choices were made for; 256 without a device), and for the frequency-major kernels slabs=S (slab buffers in LDS, 1 or 2). */
 int fc_describe_kernels(const fc_dims* dims, int32_t kind, char* buffer, size_t buffer_bytes);
 
 /* ---- filter packing -------------------------------------------------------------------- *
