@@ -259,6 +259,9 @@ SIGNATURES = {
                                   _vp, _vp]),
     'fc_mesh_affine_draw': (ctypes.c_int, [_c_int32, ctypes.c_uint64, ctypes.c_int64, _vp, _c_int32] + [ctypes.c_float] * 5 + [_vp] * 3),
     'fc_mesh_affine_apply': (ctypes.c_int, [_vp, _vp, _c_int32, _c_int32, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),
+    'fc_gradient_coefficients': (ctypes.c_int, [_vp] * 5 + [ctypes.c_double, _c_int32, _c_int32] + [_vp] * 4),
+    'fc_gradient_apply': (ctypes.c_int, [_vp] * 4 + [_c_int32] * 4 + [_vp, _vp]),
+    'fc_gradient_adjoint': (ctypes.c_int, [_vp] * 7 + [_c_int32] * 4 + [_vp, _vp]),
 }
 
 _LIB = None

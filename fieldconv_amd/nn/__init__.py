@@ -19,8 +19,9 @@ from .tangent_interpolate import TangentInterpolate
 from .tangent_max_pool import TangentMaxPool
 from .mesh_max_pool import MeshMaxPool
 from .tangent_dropout import TangentDropout
+from .tangent_gradient import TangentDivergence, TangentGradient
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
            'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval',
            'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'TangentNorm', 'TangentInterpolate',
-           'TangentMaxPool', 'MeshMaxPool', 'TangentDropout', 'MeshPool']
+           'TangentMaxPool', 'MeshMaxPool', 'TangentDropout', 'TangentGradient', 'TangentDivergence', 'MeshPool']

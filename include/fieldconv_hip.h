@@ -1122,6 +1122,48 @@ int fc_mesh_affine_draw(int32_t B, uint64_t seed, int64_t step, const int64_t* s
 int fc_mesh_affine_apply(const float* pos, const int64_t* pos_ptr, int32_t B, int32_t V, const float* M, const float* t, const int64_t* index,
                          int64_t R, float* out, void* stream);
 
+/* ---- intrinsic gradient of sample features and its adjoint, the divergence (csrc/fc_diffops.hip) --------------------------------- *
+ * A weighted least-squares fit of a linear function over each sample's ball in its own tangent plane: the meshless gradient.  It
+ * maps real features to complex ones (the gradient as a complex number in the sample's frame) with complex coefficients that depend
+ * on the geometry alone, so it is a sparse operator built once per mesh.
+ *
+ * fc_gradient_coefficients   rowptr (n+1) / col (n_slots) int32: a CSR by QUERY sample; logMag, logAng (n_slots) float32 in slot
+ *         order: slot e of row a holds the polar coordinates of log_a(col[e]) in a's frame; w (n) float32, the integration weights,
+ *         or NULL for 1.  With p_e = fl(m_e * cosf(theta_e)), q_e = fl(m_e * sinf(theta_e)), omega_e = w[col[e]]:
+ *           active   slot e iff m_e > 0 and finite, theta_e finite, col[e] in [0, n), omega_e > 0 and finite.  An inactive slot (a
+ *                    row [a, a], a zero-weight neighbour) takes part in no sum, reads nothing out of range, and has coef = 0 exactly.
+ *           moments  A11 = sum omega p p, A12 = sum omega p q, A22 = sum omega q q over the active slots, det = A11 A22 - A12 A12,
+ *                    tr = A11 + A22.  valid[a] = 1 iff det > rcond tr tr (rcond rounded once to float32; det / tr^2 <= 1/4 bounds
+ *                    the ratio of the two eigenvalues of the fit), else 0.
+ *           coef[e]  = (omega_e / det) ((A22 p_e - A12 q_e) + i (A11 q_e - A12 p_e)) on a valid row, diag[a] = sum_e coef[e].  On an
+ *                    invalid row (empty, one neighbour, collinear neighbours, a NaN among the sums) every coef and diag are 0.
+ *         coef (n_slots) and diag (n) complex64 (interleaved), valid (n) uint8.  One wavefront owns one row.  Every sum runs in this
+ *         order, fixed by the row's length alone: lane l adds the terms of slots e0 + l, e0 + l + 64, ... to a zero in ascending
+ *         order, then the 64 partial sums are folded p[l] += p[l + 32], p[l] += p[l + 16], ..., p[0] += p[1].  Every operation is a
+ *         float32 operation rounded on its own; cosf and sinf are the device library's, so the result is accurate to a few units in
+ *         the last place of p and q and NOT bit-exact against another library.  0 <= rcond <= 1, else FC_ERR_BAD_ARGUMENT.
+ * fc_gradient_apply          x (n, C) real, y (n, C) complex (interleaved), dtype FC_F32 (coef complex64) / FC_F64 (coef complex128:
+ *         the CALLER casts the coefficients to x's scalar type):  y[a, c] = sum_e coef[e] * fl(x[col[e], c] - x[a, c]) over the slots
+ *         of row a, added to a zero in ascending slot order.  A constant x gives exactly 0; a row without slots is written as zero.
+ * fc_gradient_adjoint        on the TRANSPOSED CSR rowptr_t (n+1) / col_t (n_slots; the query row of a slot) / coef_t (n_slots), and
+ *         diag (n): g (n, C) complex, gx (n, C) real,
+ *           gx[i, c] = so[i] * ((sum_t Re(conj(coef_t[t]) si[col_t[t]] g[col_t[t], c])) - Re(conj(diag[i]) si[i] g[i, c]))
+ *         the t sum added to a zero in ascending transposed-slot order.  scale_in = si and scale_out = so are (n) real of g's scalar
+ *         type or NULL for 1: si multiplies g's rows as they are read, so the result's rows.  With si = w and so = -1 / w this is
+ *         the divergence -W^-1 G^T W in one launch.
+ * apply / adjoint: one launch each; one lane owns one piece of an output row (two channels in float32 when C is even and x, y (g, gx)
+ * lie on 8-byte boundaries, else one), the lanes across one source row are contiguous.  rowptr entries are clamped to [0, n_slots]
+ * and to the row's own start; a slot whose col lies outside [0, n) contributes nothing and reads nothing out of range.  C >= 1 is
+ * arbitrary.  Entries are aligned as in the max-pooling section (not checked).  No atomics: the same bits on every run.  No workspace,
+ * no allocation or synchronisation inside. */
+int fc_gradient_coefficients(const int32_t* rowptr, const int32_t* col, const float* logMag, const float* logAng, const float* w, double rcond,
+                             int32_t n, int32_t n_slots, void* coef, void* diag, uint8_t* valid, void* stream);
+int fc_gradient_apply(const void* x, const int32_t* rowptr, const int32_t* col, const void* coef, int32_t n, int32_t n_slots, int32_t C,
+                      int32_t dtype, void* y, void* stream);
+int fc_gradient_adjoint(const void* g, const int32_t* rowptr_t, const int32_t* col_t, const void* coef_t, const void* diag,
+                        const void* scale_in, const void* scale_out, int32_t n, int32_t n_slots, int32_t C, int32_t dtype, void* gx,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
