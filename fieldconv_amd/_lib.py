@@ -262,6 +262,12 @@ SIGNATURES = {
     'fc_gradient_coefficients': (ctypes.c_int, [_vp] * 5 + [ctypes.c_double, _c_int32, _c_int32] + [_vp] * 4),
     'fc_gradient_apply': (ctypes.c_int, [_vp] * 4 + [_c_int32] * 4 + [_vp, _vp]),
     'fc_gradient_adjoint': (ctypes.c_int, [_vp] * 7 + [_c_int32] * 4 + [_vp, _vp]),
+    'fc_diffusion_lds_rows': (_c_int32, []),
+    'fc_diffusion_coefficients': (ctypes.c_int, [_vp] * 6 + [ctypes.c_double] + [_c_int32] * 3 + [_vp] * 5),
+    'fc_diffusion_apply': (ctypes.c_int, [_vp] * 7 + [_c_int32] * 5 + [_vp, _vp]),
+    'fc_diffusion_workspace_bytes': (_sz, [_c_int32] * 7),
+    'fc_diffusion_solve': (ctypes.c_int, [_vp] * 8 + [_c_int32] * 10 + [_vp] * 4 + [_sz, _vp]),
+    'fc_diffusion_time_gradient': (ctypes.c_int, [_vp] * 3 + [_c_int32] * 5 + [_vp, _vp, _sz, _vp]),
 }
 
 _LIB = None

@@ -13,7 +13,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 OUT_DIR = os.path.join(PKG, '_native')
 LIB_PATH = os.path.join(OUT_DIR, 'libfieldconv_hip.so')
-SOURCES = ['fc_api.hip', 'fc_pack.hip', 'fc_forward.hip', 'fc_forward_split.hip', 'fc_forward_ring.hip', 'fc_backward.hip', 'fc_backward_split.hip', 'fc_generic.hip', 'fc_cgemm.hip', 'fc_wide.hip', 'fc_blocks.hip', 'fc_pointwise.hip', 'fc_pointwise_f64.hip', 'fc_echo.hip', 'fc_trans_field.hip', 'fc_lift_echo_generic.hip', 'fc_head.hip', 'fc_graph.hip', 'fc_precomp.hip', 'fc_optim.hip', 'fc_support.hip', 'fc_loss.hip', 'fc_segment.hip', 'fc_match.hip', 'fc_linear_ce.hip', 'fc_geodesic.hip', 'fc_geodesic_fps.hip', 'fc_logmap.hip', 'fc_mesh_graph.hip', 'fc_transfer.hip', 'fc_norm.hip', 'fc_interp.hip', 'fc_maxpool.hip', 'fc_dropout.hip', 'fc_augment.hip', 'fc_diffops.hip']
+SOURCES = ['fc_api.hip', 'fc_pack.hip', 'fc_forward.hip', 'fc_forward_split.hip', 'fc_forward_ring.hip', 'fc_backward.hip', 'fc_backward_split.hip', 'fc_generic.hip', 'fc_cgemm.hip', 'fc_wide.hip', 'fc_blocks.hip', 'fc_pointwise.hip', 'fc_pointwise_f64.hip', 'fc_echo.hip', 'fc_trans_field.hip', 'fc_lift_echo_generic.hip', 'fc_head.hip', 'fc_graph.hip', 'fc_precomp.hip', 'fc_optim.hip', 'fc_support.hip', 'fc_loss.hip', 'fc_segment.hip', 'fc_match.hip', 'fc_linear_ce.hip', 'fc_geodesic.hip', 'fc_geodesic_fps.hip', 'fc_logmap.hip', 'fc_mesh_graph.hip', 'fc_transfer.hip', 'fc_norm.hip', 'fc_interp.hip', 'fc_maxpool.hip', 'fc_dropout.hip', 'fc_augment.hip', 'fc_diffops.hip', 'fc_diffusion.hip']
 HEADERS = ['fc_common.hpp', 'fc_pair.hpp', 'fc_kernels.hpp', 'fc_tile.hpp', 'fc_forward_kernels.hpp', 'fc_forward_ring.hpp', 'fc_forward_route.hpp', 'fc_backward_kernels.hpp', 'fc_backward_stream.hpp', 'fc_geodesic_relax.hpp', 'fc_segment.hpp', 'fc_select.hpp', 'fc_workspace.hpp', 'fc_philox.hpp', os.path.join('..', '..', 'include', 'fieldconv_hip.h')]
 # -fno-slp-vectorize: keep the stencil FMAs as v_fma_f32 with a direct SGPR operand; packed
 # v_pk_fma_f32 needs SGPR pairs built with s_mov and saturates the CU's single scalar ALU.

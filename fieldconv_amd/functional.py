@@ -1146,3 +1146,4 @@ from .norm import tangent_norm          # noqa: E402,F401  (csrc/fc_norm.hip)
 from .dropout import philox_words, tangent_dropout          # noqa: E402,F401  (csrc/fc_dropout.hip, fc_philox.hpp)
 from .augment import mesh_affine, random_mesh_affine          # noqa: E402,F401  (csrc/fc_augment.hip)
 from .diffops import GradientPlan, gradient_plan, laplacian, tangent_divergence, tangent_gradient          # noqa: E402,F401  (csrc/fc_diffops.hip)
+from .diffusion import DiffusionPlan, connection_laplacian, diffusion_plan, heat_diffuse          # noqa: E402,F401  (csrc/fc_diffusion.hip)

@@ -20,8 +20,9 @@ from .tangent_max_pool import TangentMaxPool
 from .mesh_max_pool import MeshMaxPool
 from .tangent_dropout import TangentDropout
 from .tangent_gradient import TangentDivergence, TangentGradient
+from .tangent_diffusion import TangentDiffusion
 
 __all__ = ['TangentNonLin', 'TangentLin', 'TangentPerceptron', 'TransField', 'FieldConv', 'ECHO', 'LiftBlock',
            'FCResNetBlock', 'ECHOBlock', 'LabelSmoothingLoss', 'TwinLoss', 'TwinEval',
            'LinearCrossEntropy', 'vertex_accuracy', 'TangentPool', 'TangentUnpool', 'TangentNorm', 'TangentInterpolate',
-           'TangentMaxPool', 'MeshMaxPool', 'TangentDropout', 'TangentGradient', 'TangentDivergence', 'MeshPool']
+           'TangentMaxPool', 'MeshMaxPool', 'TangentDropout', 'TangentGradient', 'TangentDivergence', 'TangentDiffusion', 'MeshPool']

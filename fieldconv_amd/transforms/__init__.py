@@ -13,9 +13,10 @@ from .coarsen_samples import CoarsenSamples
 from .samples_to_vertices import SamplesToVertices
 from .random_mesh_affine import RandomMeshAffine
 from .gradient_operator import GradientOperator
+from .diffusion_operator import DiffusionOperator
 
 __all__ = ['FCPrecomp', 'NormalizeArea', 'NormalizeAxes', 'SupportGraph', 'farthest_point_sample', 'load_precomp', 'radius_edges',
            'save_precomp', 'farthest_point_sample_batched', 'radius_edges_batched', 'SampleWeights', 'geodesic_distances',
            'mesh_edge_graph', 'nearest_sample', 'sample_weights', 'GeodesicSupportGraph', 'geodesic_farthest_point_sample',
            'geodesic_farthest_point_sample_batched', 'geodesic_radius_edges', 'ComputeLogXPort', 'computeLogXPort', 'log_map_transport',
-           'vertex_frames', 'CoarsenSamples', 'SamplesToVertices', 'RandomMeshAffine', 'GradientOperator']
+           'vertex_frames', 'CoarsenSamples', 'SamplesToVertices', 'RandomMeshAffine', 'GradientOperator', 'DiffusionOperator']

@@ -1164,6 +1164,69 @@ int fc_gradient_adjoint(const void* g, const int32_t* rowptr_t, const int32_t* c
                         const void* scale_in, const void* scale_out, int32_t n, int32_t n_slots, int32_t C, int32_t dtype, void* gx,
                         void* stream);
 
+/* ---- heat diffusion of sample features: connection Laplacian and on-device CG (csrc/fc_diffusion.hip) ---------------------------- *
+ * The stiffness matrix S = 1/2 D^H C D of the support graph, (D v)[e] = v[b] - u_e v[a] for a row e = [a, b] with transport u_e, as a
+ * merged CSR of 2 E entries: row i holds one entry per row [i, b] (col b, the OUT entries, in ascending e), then one per row [a, i]
+ * (col a, the IN entries, in ascending e).  The caller lays the pattern out; edge[k] is e for an in entry and -e - 1 for an out entry.
+ *
+ * fc_diffusion_coefficients   rowptr (n+1), col, edge (n_entries) int32; logMag (n_edges) float32; xp (n_edges) complex64; w (n) float32
+ *         or NULL for 1; h > 0.  four_h = fl32(4 h) and norm = fl32(4 pi h^2) are rounded once from double.  A row e is ACTIVE iff
+ *         a != b, m_e = logMag[e] is finite and > 0, xp[e] is finite, w_a and w_b are finite and > 0.  On an active row
+ *           c_e = ((w_a * w_b) * expf(-((m_e * m_e) / four_h))) / norm,   g_e = -0.5 * c_e
+ *           coef = (g_e Re u_e, -(g_e Im u_e)) for the out entry and (g_e Re u_e, g_e Im u_e) for the in entry;  coef_real = g_e
+ *         and on an inactive one both are exactly 0 (its entries stay in the pattern).  Per row, over its active entries in entry order,
+ *         added to a zero:  diag[i] = 0.5 * sum (c_e * (Re u_e Re u_e + Im u_e Im u_e) for an out entry, c_e for an in entry),
+ *         diag_real[i] = 0.5 * sum c_e.  coef (n_entries) complex64, coef_real (n_entries), diag, diag_real (n) float32.  Every
+ *         operation is a float32 operation rounded on its own; expf is the device library's: accurate to a few units in the last
+ *         place, NOT bit-exact against another library.  The two entries of a row are exact conjugates: S is Hermitian to the bit.
+ *         One thread per row of the matrix, one launch, no atomics.
+ * fc_diffusion_apply          x, y (n, C) of dtype FC_F32 / FC_F64, is_complex 1 (interleaved pairs; coef complex) or 0 (coef real);
+ *         coef, diag, scale_in, scale_out in x's scalar type (the CALLER casts):
+ *           y[i, c] = so[i] * ((sum_k coef[k] * (si[col[k]] * x[col[k], c])) + diag[i] * (si[i] * x[i, c]))
+ *         the k sum over the row's entries added to a zero in entry order; si, so (n) or NULL for 1.  so = -1 / w is the Laplacian
+ *         -W^-1 S, si = -1 / w its adjoint.  One lane per (row, channel), one launch, no atomics.
+ * fc_diffusion_solve          per mesh b (rows ptr[b] .. ptr[b+1] - 1; ptr (B+1) int64 DEVICE memory, or NULL: B = 1, all n rows) and
+ *         channel c, exactly `iters` (1 .. 1024) steps of Jacobi-preconditioned conjugate gradients on (W + t_c S) y = rhs:
+ *           mode 0   rhs = W x,  y0 = x,  out = y              mode 1   rhs = x,  y0 = x / w (0 where w <= 0),  out = W y,  lam = y
+ *           P_i = w_i + t_c d_i                  (z = r / P where P > 0, else 0)
+ *           r0 = rhs - (W + t S) y0      z0 = r0 / P      p0 = z0      rz = Re<r0, z0>
+ *           repeat iters times:
+ *               q = (W + t S) p                  pq = Re<p, q>
+ *               alpha = rz / pq if pq > 0 else 0
+ *               y += alpha p      r -= alpha q      (both skipped when alpha == 0)      z = r / P
+ *               rz' = Re<r, z>    beta = rz' / rz if rz > 0 else 0
+ *               p = z + beta p    rz = rz'
+ *         with ((W + t S) v)[i] = w_i v_i + t_c ((sum_k coef[k] v[col[k]]) + d_i v_i), the k sum as in apply.  Vectors and every
+ *         operation on them are in x's scalar type, each rounded on its own; alpha and beta are double quotients rounded once.  The
+ *         inner products are double: thread l of 1024 adds the terms of the mesh's rows l, l + 1024, ... in ascending order to a
+ *         zero, the 64 lanes of a wavefront are folded v[l] += v[l + 32], v[l + 16], ..., v[l + 1], and the 16 wavefronts' sums are
+ *         added in index order.  t (C) in x's scalar type: t_c = 0 gives out = x bit for bit (mode 0); a negative or non-finite t_c
+ *         gives NaN in column c of out, lam and resid and touches nothing else.  resid (B, C) in x's scalar type or NULL: sqrt(rz) at
+ *         exit.  lam (n, C) or NULL.
+ *         One launch: a workgroup of 1024 threads owns one mesh and 16 bytes of a row (4 float32, 2 float64 / complex64 or
+ *         1 complex128 channel) through all iterations.  The search direction p lives in LDS when max_rows <= fc_diffusion_lds_rows()
+ *         and where == 0, else (where == 1 forces it) in the workspace; the loop and the bits are the same.  max_rows: the largest
+ *         mesh (n without ptr); a range that ptr makes longer is cut to it.  No atomics, no cooperative launch, nothing waits on another workgroup.  Entries whose col lies
+ *         outside the row's mesh contribute nothing.  Workspace: the query below; FC_ERR_WORKSPACE when missing or smaller.
+ * fc_diffusion_time_gradient  gt[c] = -sum_b (sum over the rows i of mesh b of Re(conj(lam[i, c]) sy[i, c])), in double and in a
+ *         fixed order (thread (j, l) of 16 x 64 adds the rows j, j + 16, ... of a channel, the 16 sums are added in index order,
+ *         then the meshes in index order), rounded once to x's scalar type.  Two launches.  Workspace: 8 B C bytes rounded up to 256.
+ * No allocation or synchronisation inside. */
+int32_t fc_diffusion_lds_rows(void);
+int fc_diffusion_coefficients(const int32_t* rowptr, const int32_t* col, const int32_t* edge, const float* logMag, const void* xp,
+                              const float* w, double h, int32_t n, int32_t n_edges, int32_t n_entries, void* coef, float* coef_real,
+                              float* diag, float* diag_real, void* stream);
+int fc_diffusion_apply(const void* x, const int32_t* rowptr, const int32_t* col, const void* coef, const void* diag, const void* scale_in,
+                       const void* scale_out, int32_t n, int32_t n_entries, int32_t C, int32_t dtype, int32_t is_complex, void* y,
+                       void* stream);
+size_t fc_diffusion_workspace_bytes(int32_t n, int32_t B, int32_t C, int32_t dtype, int32_t is_complex, int32_t max_rows, int32_t where);
+int fc_diffusion_solve(const void* x, const void* t, const void* w, const void* diag, const int32_t* rowptr, const int32_t* col,
+                       const void* coef, const int64_t* ptr, int32_t n, int32_t n_entries, int32_t B, int32_t C, int32_t max_rows,
+                       int32_t dtype, int32_t is_complex, int32_t iters, int32_t mode, int32_t where, void* y, void* lam, void* resid,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int fc_diffusion_time_gradient(const void* lam, const void* sy, const int64_t* ptr, int32_t n, int32_t B, int32_t C, int32_t dtype,
+                               int32_t is_complex, void* gt, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
